@@ -9,6 +9,12 @@ Single GPU:   python bench.py --gpus 1 --steps 10 --warmup 3
 Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                   --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times --steps steps and prints the result
+line; nothing else. --dump-outputs DIR also writes what the last timed
+step computed as DIR/<name>.npy (same arguments -> same inputs, so two
+builds can be compared output for output). --full is reserved for any
+measurement beyond the headline figure; there is none at present.
+
 Rank 0 prints exactly ONE JSON line on stdout.
 """
 from __future__ import annotations
@@ -49,8 +55,34 @@ def stage_tunableop() -> None:
     os.environ["PYTORCH_TUNABLEOP_VERBOSE"] = "0"
 
 
+DUMP_SAMPLE_ELEMS = 1 << 22   # 16 MB of float32 — far under the 64 MB cap
+DUMP_SAMPLE_SEED = 20240521
+
+
+def dump_outputs(out_dir: str, trainer, last_loss) -> None:
+    """Write what the last timed train_step() handed its caller: the loss
+    it returned and the weights it left behind. The flat weight buffer of
+    the 8B model is 16 GB, so a fixed, seeded, sorted sample of its
+    elements is written (all of it when it is small enough)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if last_loss is not None:
+        np.save(os.path.join(out_dir, "loss.npy"),
+                last_loss.detach().float().cpu().reshape(1).numpy())
+    flat = trainer.store.flat_param
+    if flat.numel() > DUMP_SAMPLE_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE_ELEMS,),
+                            generator=g).sort().values
+        flat = flat.index_select(0, idx.to(flat.device))
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            flat.detach().float().cpu().numpy())
+    log(f"[bench] wrote loss.npy and params_sample.npy to {out_dir}")
+
+
 def main() -> None:
-    ap = argparse.ArgumentParser()
+    ap =argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -71,7 +103,19 @@ def main() -> None:
                     help="EXPERIMENTAL: hipGraph step capture (replay of "
                          "large-seq graphs currently faults in the ROCm "
                          "runtime — validated only at small scale)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step computed (its loss and a fixed seeded sample "
+                         "of the updated weights) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond "
+                         "the headline figure (nothing at present: a plain "
+                         "run already does only setup, warmup, the timed "
+                         "steps and the result line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (it is the number of timed "
+                 "steps that ms_per_step averages over)")
 
     if os.environ.get("BENCH_DEBUG"):
         import faulthandler
@@ -133,8 +177,9 @@ def main() -> None:
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last_loss = None
     for i in range(args.steps):
-        trainer.train_step()
+        last_loss = trainer.train_step()
         if os.environ.get("BENCH_DEBUG"):
             log(f"[bench] step {i} queued")
     if on_gpu:
@@ -146,6 +191,9 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         dist.barrier()
+
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, trainer, last_loss)
 
     # with TP, tp ranks share one replica: whole-job tokens count replicas
     n_replicas = n_gpus // max(args.tp, 1)

@@ -50,6 +50,40 @@ def test_attn_fwd_matches_sdpa(B, H, S):
         f"lse max err {(lse[0, 0] - lse_ref).abs().max()}"
 
 
+def test_attn_and_rmsnorm_grads_repeat_bit_exact():
+    """The same inputs give the same bits every time: the attention kernels
+    only read LDS tiles their own wave waited for or a barrier published,
+    and the RMSNorm weight gradient is summed in a fixed order (no
+    atomics). GQA shape with more than one 256-row q block and an RMSNorm
+    row count that spans several reduce chunks."""
+    from trainingjob_operator_amd.ops import fused_rmsnorm
+    from trainingjob_operator_amd.ops.attention import flash_attention
+    B, H, HKV, S, D = 2, 8, 2, 1024, 128
+    g = torch.Generator(device=DEV).manual_seed(7)
+    q0 = (torch.randn(B, H, S, D, device=DEV, generator=g) * 0.5).bfloat16()
+    k0 = (torch.randn(B, HKV, S, D, device=DEV, generator=g) * 0.5).bfloat16()
+    v0 = (torch.randn(B, HKV, S, D, device=DEV, generator=g) * 0.5).bfloat16()
+    go = (torch.randn(B, H, S, D, device=DEV, generator=g) * 0.5).bfloat16()
+    x0 = torch.randn(4100, 4096, device=DEV, generator=g).bfloat16()
+    w0 = torch.randn(4096, device=DEV, generator=g).bfloat16()
+    gy = torch.randn(4100, 4096, device=DEV, generator=g).bfloat16()
+
+    def once():
+        q, k, v = (t.clone().requires_grad_() for t in (q0, k0, v0))
+        out = flash_attention(q, k, v)
+        out.backward(go)
+        x, w = x0.clone().requires_grad_(), w0.clone().requires_grad_()
+        y, _ = fused_rmsnorm(x, w)
+        y.backward(gy)
+        return out.detach(), q.grad, k.grad, v.grad, x.grad, w.grad
+
+    first = once()
+    for _ in range(3):
+        for name, a, b in zip(("out", "dq", "dk", "dv", "dx", "dw"),
+                              first, once()):
+            assert torch.equal(a, b), name
+
+
 def test_attn_fwd_strided_inputs():
     """The model passes [B,S,H,D]-permuted views; strides must be honored."""
     from trainingjob_operator_amd.ops.attention import flash_attention_fwd_only

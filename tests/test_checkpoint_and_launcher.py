@@ -178,6 +178,46 @@ def test_bench_contract_two_ranks(tmp_path):
     assert rec["value"] > 0 and rec["config"]["parallelism"] == "dp2"
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's loss and weight sample
+    as float32 .npy files, identical from run to run for the same
+    arguments; the result line carries ms_per_step; --full is accepted."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE")}
+    # run on the CPU path everywhere: it is bit-reproducible, while the GPU
+    # kernels fold some gradients with fp32 atomics in arrival order
+    env["HIP_VISIBLE_DEVICES"] = env["CUDA_VISIBLE_DEVICES"] = ""
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"),
+             "--gpus", "1", "--steps", "3", "--warmup", "1",
+             "--model", "llama-tiny", "--seq-len", "32",
+             "--micro-batch", "1", "--grad-accum", "1",
+             "--dump-outputs", str(out)] + extra,
+            capture_output=True, text=True, timeout=300, cwd=root, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1500:]
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["loss.npy", "params_sample.npy"]
+        arrs = {f: np.load(out / f) for f in os.listdir(out)}
+        for a in arrs.values():
+            assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert arrs["loss.npy"].shape == (1,)
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_sigusr1_checkpoints_on_demand(tmp_path):
     """SIGUSR1 forces a checkpoint at the next step boundary (planned
     maintenance hook), independent of --ckpt-every."""

@@ -788,8 +788,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const u16* vgp[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int idx = i * NT + tid;
-    const int L = idx * 16;
+    // wave w stages rows 8w..8w+7 — exactly the rows its own lanes
+    // transpose below, so the wave's own counted vmcnt covers them (rows
+    // staged by another wave are only guaranteed landed after a barrier)
+    const int L = (tid & ~63) * 32 + i * 1024 + (tid & 63) * 16;
     const int kr = L >> 8;
     const int kin = (((L & 255) ^ ((kr & 15) << 4)) >> 1);
     kgp[i] = kbase + (long)kr * k_ss + kin;
@@ -797,17 +799,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   }
   const long kstep = (long)V6_BN * k_ss;
   const long vstep = (long)V6_BN * v_ss;
-  const int lslot = (tid & ~63) * 8;
+  const int lslot = (tid & ~63) * 16;
 
 #define DQ_GLDS(SLOT)                                                       \
   _Pragma("unroll")                                                         \
   for (int i = 0; i < 2; ++i) {                                             \
     __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)kgp[i], (u32*)&DQ_K(SLOT)[i * NT * 8 + lslot],          \
+        (const u32*)kgp[i], (u32*)&DQ_K(SLOT)[i * 512 + lslot],          \
         16, 0, 0);                                                          \
     kgp[i] += kstep;                                                        \
     __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)vgp[i], (u32*)&DQ_VR(SLOT)[i * NT * 8 + lslot],         \
+        (const u32*)vgp[i], (u32*)&DQ_VR(SLOT)[i * 512 + lslot],         \
         16, 0, 0);                                                          \
     vgp[i] += vstep;                                                        \
   }
@@ -833,6 +835,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
   v7_barrier();
   DQ_TRANSPOSE(0, DQ_KT(0))
+  v7_barrier();   // tile 0 reads every wave's share of KT[0]
 
   for (int t = 0; t < n_tiles; ++t) {
     const int kv0 = t * V6_BN;
@@ -1442,9 +1445,10 @@ extern "C" int attn_bwd(void* stream, const void* q, const void* k,
 //     b32 writes per thread) from the landed row image — no global
 //     staging registers at all;
 //   * barriers are RAW s_barrier (guide: "3-buffer glds + raw barrier,
-//     counted vmcnt only"), two per tile: one after the counted
-//     vmcnt making slot t+1 visible for the transpose, one at tile end
-//     guarding ring reuse.
+//     counted vmcnt only"), one per tile, at tile end, guarding ring
+//     reuse and publishing the next transposed image. The transpose
+//     itself needs no barrier: every wave stages by glds exactly the
+//     rows it transposes, so its own counted vmcnt covers them.
 // ===========================================================================
 
 __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
@@ -1502,8 +1506,10 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   const u16* vgp[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int idx = i * NT + tid;
-    const int L = idx * 16;
+    // wave w stages rows 8w..8w+7 — exactly the rows its own lanes
+    // transpose below, so the wave's own counted vmcnt covers them (rows
+    // staged by another wave are only guaranteed landed after a barrier)
+    const int L = (tid & ~63) * 32 + i * 1024 + (tid & 63) * 16;
     const int kr = L >> 8;
     const int kin = (((L & 255) ^ ((kr & 15) << 4)) >> 1);
     kgp[i] = kbase + (long)kr * k_ss + kin;
@@ -1511,17 +1517,17 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   }
   const long kstep = (long)V6_BN * k_ss;
   const long vstep = (long)V6_BN * v_ss;
-  const int lslot = (tid & ~63) * 8;          // wave-uniform u16 base
+  const int lslot = (tid & ~63) * 16;         // wave-uniform u16 base
 
 #define V7_GLDS(SLOT)                                                       \
   _Pragma("unroll")                                                         \
   for (int i = 0; i < 2; ++i) {                                             \
     __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)kgp[i], (u32*)&LDSK(SLOT)[i * NT * 8 + lslot],          \
+        (const u32*)kgp[i], (u32*)&LDSK(SLOT)[i * 512 + lslot],          \
         16, 0, 0);                                                          \
     kgp[i] += kstep;                                                        \
     __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)vgp[i], (u32*)&LDSVR(SLOT)[i * NT * 8 + lslot],         \
+        (const u32*)vgp[i], (u32*)&LDSVR(SLOT)[i * 512 + lslot],         \
         16, 0, 0);                                                          \
     vgp[i] += vstep;                                                        \
   }
@@ -1549,7 +1555,9 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
   v7_barrier();
   V7_TRANSPOSE(0, LDSVT(0))
-  // Vt[0] visible to every wave at the first in-loop barrier below
+  // tile 0's PV reads every wave's share of Vt[0] before the first in-loop
+  // barrier (that one sits at the END of tile 0), so publish it here
+  v7_barrier();
 
   for (int t = 0; t < n_tiles; ++t) {
     const int kv0 = t * V6_BN;

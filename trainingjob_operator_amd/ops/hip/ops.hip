@@ -321,22 +321,27 @@ __global__ void rmsnorm_bwd_generic_kernel(
   }
 }
 
-__global__ void rmsnorm_dw_reduce_kernel(const float* __restrict__ dw_partial,
+__global__ void rmsnorm_dw_reduce_kernel(float* __restrict__ dw_partial,
                                          int n_partials,
                                          float* __restrict__ dw_out, int H,
-                                         int rows_per_block) {
+                                         int rows_per_block, int row_step) {
   // 2D grid: x tiles the H columns, y tiles the partial rows. Each block
-  // sums its row chunk for its 256 columns and atomically folds into
-  // dw_out (zero-initialized). The 1D one-thread-per-column version had
-  // only H/256 blocks and measured 66 GB/s / 242 us per call on MI355X.
+  // sums its row chunk (every row_step-th row) for its 256 columns. The 1D
+  // one-thread-per-column version had only H/256 blocks and measured
+  // 66 GB/s / 242 us per call on MI355X. With dw_out == nullptr (first
+  // pass) the chunk sum is stored back into the chunk's first partial row
+  // — read and written by this thread alone — and a second single-row
+  // launch sums those rows in a fixed order into dw_out. No atomics: the
+  // float sum order, and so the result, is the same on every run.
   const int h = blockIdx.x * blockDim.x + threadIdx.x;
   if (h >= H) return;
   const int p0 = blockIdx.y * rows_per_block;
   int p1 = p0 + rows_per_block;
   if (p1 > n_partials) p1 = n_partials;
   float acc = 0.f;
-  for (int p = p0; p < p1; ++p) acc += dw_partial[(long)p * H + h];
-  atomicAdd(&dw_out[h], acc);
+  for (int p = p0; p < p1; p += row_step) acc += dw_partial[(long)p * H + h];
+  if (dw_out) dw_out[h] = acc;
+  else if (p0 < n_partials) dw_partial[(long)p0 * H + h] = acc;
 }
 
 // ===========================================================================
@@ -1396,7 +1401,7 @@ int rmsnorm_bwd(void* stream, const void* dy, const void* res_out,
   return 0;
 }
 
-int rmsnorm_dw_reduce(void* stream, const void* dw_partial, long n_partials,
+int rmsnorm_dw_reduce(void* stream, void* dw_partial, long n_partials,
                       void* dw_f32, int H) {
   if (H <= 0 || n_partials <= 0) return -1;
   // aim for ~1024 blocks total to fill 256 CUs; bx >= 1 always (the round-1
@@ -1406,10 +1411,15 @@ int rmsnorm_dw_reduce(void* stream, const void* dw_partial, long n_partials,
   if (ny < 1) ny = 1;
   if (ny > n_partials) ny = (int)n_partials;
   const int rows_per_block = (int)((n_partials + ny - 1) / ny);
-  dim3 grid(bx, ny), block(BLOCK);
-  hipLaunchKernelGGL(rmsnorm_dw_reduce_kernel, grid, block, 0, STREAM,
-                     (const float*)dw_partial, (int)n_partials, (float*)dw_f32,
-                     H, rows_per_block);
+  dim3 block(BLOCK);
+  // pass 1 folds each row chunk into its first row (dw_partial is scratch
+  // owned by the caller); pass 2 sums the chunk heads in order
+  hipLaunchKernelGGL(rmsnorm_dw_reduce_kernel, dim3(bx, ny), block, 0, STREAM,
+                     (float*)dw_partial, (int)n_partials, (float*)nullptr,
+                     H, rows_per_block, 1);
+  hipLaunchKernelGGL(rmsnorm_dw_reduce_kernel, dim3(bx, 1), block, 0, STREAM,
+                     (float*)dw_partial, (int)n_partials, (float*)dw_f32,
+                     H, (int)n_partials, rows_per_block);
   return 0;
 }
 
