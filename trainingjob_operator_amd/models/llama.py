@@ -7,7 +7,11 @@ Design (per /opt/skills/guides/MI355X_MICROARCH.md):
   * residual-add + RMSNorm fused to one HBM round trip (ops.fused_rmsnorm);
     SwiGLU and RoPE fused likewise; loss is a fused streaming CE over the
     [T, 128256] logits.
-  * attention = torch SDPA (flash path on ROCm) with grouped-query KV.
+  * attention = the hand-written MFMA flash kernels (ops/attention.py,
+    forward and backward, native grouped-query KV). At head_dim 128 and
+    S % 256 == 0 they run directly on the packed QKV projection output
+    (one RoPE launch per direction, no layout copies); torch SDPA covers
+    the remaining shapes (CPU, small head_dim, decode).
   * activations optionally checkpointed per block; with 288 GB HBM3E per
     GPU the default keeps activations resident (checkpointing off) — flip
     it on only for long-sequence configs.
@@ -72,6 +76,23 @@ def _proj(x, linear):
 from .config import LlamaConfig
 
 
+def _use_packed_attention(qkv: torch.Tensor, cfg: LlamaConfig) -> bool:
+    """Packed RoPE+attention (ops.attention.packed_rope_attention) runs
+    where the native v7 forward and native backward would run anyway: GPU
+    bf16, head_dim 128, S % 256 == 0, native kernels selected for both
+    directions, GQA not expanded by hand. The fp8 projection output and
+    every other case keep the unpacked path. AITJ_ATTN_PACKED=0 forces the
+    unpacked path (A/B knob)."""
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and cfg.head_dim == 128 and qkv.shape[1] % 256 == 0
+            and os.environ.get("AITJ_SDPA_BACKEND", "auto") in ("auto",
+                                                                 "native")
+            and not os.environ.get("AITJ_DISABLE_GQA")
+            and os.environ.get("AITJ_ATTN_BWD") != "aten"
+            and os.environ.get("AITJ_ATTN_PACKED", "1") != "0"
+            and not fp8_enabled())
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -89,6 +110,13 @@ class Attention(nn.Module):
         B, S, H = x.shape
         cfg = self.cfg
         qkv = _proj(x, self.qkv_proj)
+        if _use_packed_attention(qkv, cfg):
+            # RoPE + attention on the packed projection output: no dense
+            # q/k copies, no output transpose copy, no cat in the backward
+            from ..ops.attention import packed_rope_attention
+            o = packed_rope_attention(qkv, inv_freq, cfg.num_heads,
+                                      cfg.num_kv_heads)
+            return _proj(o, self.o_proj)
         q, k, v = qkv.split([self.q_size, self.kv_size, self.kv_size],
                             dim=-1)
         # q/k go through the RoPE kernel, which wants dense rows

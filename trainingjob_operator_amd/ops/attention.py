@@ -113,6 +113,136 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return _NativeFlashAttention.apply(q, k, v, scale)
 
 
+# ---------------------------------------------------------------------------
+# RoPE + attention straight on the packed QKV projection output
+# ---------------------------------------------------------------------------
+
+def _bhsd_strides(row: int, D: int, S: int):
+    """(batch, head, row) strides of a head range inside packed rows of
+    `row` elements — a [B,S,heads,D] buffer read as [B,heads,S,D]."""
+    return (S * row, D, row)
+
+
+def _rope_packed(lib, x, out, inv_freq, n_tokens, n_rot, x_row, out_row,
+                 S, D, sign):
+    assert inv_freq.device == x.device and inv_freq.dtype == torch.float32, (
+        f"inv_freq must be fp32 on {x.device}, got "
+        f"{inv_freq.dtype}@{inv_freq.device}")
+    rc = lib.rope_packed(native.stream_ptr(), x.data_ptr(), out.data_ptr(),
+                         inv_freq.data_ptr(), n_tokens, n_rot, x_row,
+                         out_row, S, D, sign)
+    native.check_rc(rc, "rope_packed", f"D={D} n_rot={n_rot} row={x_row}")
+
+
+class _PackedRopeAttention(torch.autograd.Function):
+    """qkv [B,S,(H+2HKV)*128] -> o [B,S,H*128] with no layout copies: one
+    RoPE launch over the q|k head range, the v7 forward reading q/k/v and
+    writing o through strides; the backward kernels write their head
+    ranges of one dqkv buffer, un-rotated in place by one RoPE launch."""
+
+    @staticmethod
+    def forward(ctx, qkv, inv_freq, n_heads, n_kv_heads, scale):
+        B, S, W = qkv.shape
+        D = 128
+        H, HKV = n_heads, n_kv_heads
+        assert W == (H + 2 * HKV) * D
+        qkv = qkv.contiguous()
+        lib = native.load(require=True)
+        R = (H + HKV) * D
+        rot = torch.empty(B, S, R, dtype=torch.bfloat16, device=qkv.device)
+        _rope_packed(lib, qkv, rot, inv_freq, B * S, H + HKV, W, R, S, D, 1.0)
+        o = torch.empty(B, S, H * D, dtype=torch.bfloat16, device=qkv.device)
+        lse = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
+        esz = qkv.element_size()
+        st = native.stride_array(
+            _bhsd_strides(R, D, S), _bhsd_strides(R, D, S),
+            _bhsd_strides(W, D, S), _bhsd_strides(H * D, D, S))
+        rc = lib.attn_fwd_strided(
+            native.stream_ptr(), rot.data_ptr(),
+            rot.data_ptr() + H * D * esz,
+            qkv.data_ptr() + (H + HKV) * D * esz,
+            o.data_ptr(), lse.data_ptr(), st, B, H, HKV, S, scale)
+        native.check_rc(rc, "attn_fwd_strided", f"B={B} H={H} HKV={HKV} S={S}")
+        ctx.save_for_backward(rot, qkv, o, lse, inv_freq)
+        ctx.dims = (B, S, H, HKV, D)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, gout):
+        rot, qkv, o, lse, inv_freq = ctx.saved_tensors
+        B, S, H, HKV, D = ctx.dims
+        W, R = (H + 2 * HKV) * D, (H + HKV) * D
+        lib = native.load(require=True)
+        # the o_proj GEMM hands back a dense [B,S,H*D] gradient
+        dout = gout if gout.is_contiguous() else gout.contiguous()
+        delta = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
+        dqkv = torch.empty(B, S, W, dtype=torch.bfloat16, device=qkv.device)
+        esz = qkv.element_size()
+        rs, ws, os_ = (_bhsd_strides(R, D, S), _bhsd_strides(W, D, S),
+                       _bhsd_strides(H * D, D, S))
+        st = native.stride_array(rs, rs, ws, os_, os_, ws, ws, ws)
+        rc = lib.attn_bwd_strided(
+            native.stream_ptr(), rot.data_ptr(),
+            rot.data_ptr() + H * D * esz,
+            qkv.data_ptr() + (H + HKV) * D * esz,
+            o.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+            dqkv.data_ptr(), dqkv.data_ptr() + H * D * esz,
+            dqkv.data_ptr() + (H + HKV) * D * esz,
+            st, B, H, HKV, S, ctx.scale)
+        native.check_rc(rc, "attn_bwd_strided", f"B={B} H={H} HKV={HKV} S={S}")
+        _rope_packed(lib, dqkv, dqkv, inv_freq, B * S, H + HKV, W, W, S, D,
+                     -1.0)
+        return dqkv, None, None, None, None
+
+
+def packed_supported(qkv: torch.Tensor, n_heads: int, n_kv_heads: int) -> bool:
+    """Shapes the packed path covers: GPU bf16 [B,S,(H+2HKV)*128] with
+    S % 256 == 0 (the v7 forward + native backward kernels)."""
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3
+            and qkv.shape[1] % 256 == 0 and n_heads % n_kv_heads == 0
+            and qkv.shape[2] == (n_heads + 2 * n_kv_heads) * 128)
+
+
+def unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale=None):
+    """The copying composition packed_rope_attention replaces (and its
+    fallback): split, dense q/k, RoPE each, [B,h,S,D] attention, transpose
+    back. Any head_dim; native flash attention where it applies, torch
+    SDPA elsewhere."""
+    from .functional import apply_rope
+    B, S, W = qkv.shape
+    D = W // (n_heads + 2 * n_kv_heads)
+    q, k, v = qkv.split([n_heads * D, n_kv_heads * D, n_kv_heads * D], dim=-1)
+    q = q.reshape(B, S, n_heads, D).contiguous()
+    k = k.reshape(B, S, n_kv_heads, D).contiguous()
+    v = v.reshape(B, S, n_kv_heads, D)
+    q = apply_rope(q, inv_freq, S).transpose(1, 2)
+    k = apply_rope(k, inv_freq, S).transpose(1, 2)
+    v = v.transpose(1, 2)
+    if qkv.is_cuda and _supported(q, k):
+        o = flash_attention(q, k, v, scale)
+    else:
+        o = torch.nn.functional.scaled_dot_product_attention(
+            q, k, v, is_causal=True, scale=scale,
+            enable_gqa=n_heads != n_kv_heads)
+    return o.transpose(1, 2).reshape(B, S, n_heads * D)
+
+
+def packed_rope_attention(qkv: torch.Tensor, inv_freq: torch.Tensor,
+                          n_heads: int, n_kv_heads: int,
+                          scale: Optional[float] = None) -> torch.Tensor:
+    """Causal RoPE attention on the fused projection output:
+    qkv [B,S,(H+2HKV)*D] -> o [B,S,H*D]. D = 128 bf16 on the GPU with
+    S % 256 == 0 runs the copy-free packed kernels; everything else (CPU,
+    other head sizes, other S) runs the unpacked composition."""
+    if packed_supported(qkv, n_heads, n_kv_heads):
+        if scale is None:
+            scale = 1.0 / math.sqrt(128)
+        return _PackedRopeAttention.apply(qkv, inv_freq, n_heads, n_kv_heads,
+                                          scale)
+    return unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale)
+
+
 def flash_attention_fwd_only(q, k, v, scale=None):
     """Forward-only entry returning (out, lse) for tests/benchmarks."""
     if scale is None:

@@ -592,7 +592,37 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long q_sb, long q_sh, long q_ss,
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
+    long o_sb, long o_sh, long o_ss,
     int n_heads, int gqa_group, int S, float scale2);
+
+// The kernels move 16-byte vectors along D, so every stride must keep rows
+// 16-byte aligned (a multiple of 8 bf16 elements).
+static inline bool attn_strides_ok(const long* st, int n) {
+  for (int i = 0; i < n; ++i)
+    if (st[i] < 0 || st[i] % 8 != 0) return false;
+  return true;
+}
+
+// v7 launch shared by attn_fwd, attn_fwd_v7 (contiguous [B,H,S,D] out) and
+// attn_fwd_strided (out through batch/head/row strides)
+static void launch_fwd_v7(void* stream, const void* q, const void* k,
+                          const void* v, void* out, void* lse,
+                          long q_sb, long q_sh, long q_ss,
+                          long k_sb, long k_sh, long k_ss,
+                          long v_sb, long v_sh, long v_ss,
+                          long o_sb, long o_sh, long o_ss,
+                          int batch, int n_heads, int n_kv_heads, int S,
+                          float scale) {
+  const float scale2 = scale * 1.4426950408889634f;   // fold log2(e)
+  dim3 grid(S / 256, n_heads, batch), block(512);
+  hipLaunchKernelGGL(attn_fwd_v7_kernel, grid, block, 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     (const u16*)q, (const u16*)k, (const u16*)v,
+                     (u16*)out, (float*)lse, q_sb, q_sh, q_ss,
+                     k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
+                     o_sb, o_sh, o_ss, n_heads,
+                     n_heads / n_kv_heads, S, scale2);
+}
 
 extern "C" int attn_fwd(void* stream, const void* q, const void* k,
                         const void* v, void* out, void* lse,
@@ -612,13 +642,10 @@ extern "C" int attn_fwd(void* stream, const void* q, const void* k,
     if (S % 256 == 0) {
       // v7: 3-deep all-glds pipeline, single raw barrier per tile
       // (299 us vs v6's 346 at B1H32S4096; aotriton 425)
-      dim3 grid(S / 256, n_heads, batch), block(512);
-      hipLaunchKernelGGL(attn_fwd_v7_kernel, grid, block, 0,
-                         reinterpret_cast<hipStream_t>(stream),
-                         (const u16*)q, (const u16*)k, (const u16*)v,
-                         (u16*)out, (float*)lse, q_sb, q_sh, q_ss,
-                         k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, n_heads,
-                         n_heads / n_kv_heads, S, scale2);
+      launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
+                    k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
+                    (long)n_heads * S * ATTN_D, (long)S * ATTN_D, ATTN_D,
+                    batch, n_heads, n_kv_heads, S, scale);
       return 0;
     }
     dim3 grid(S / 128, n_heads, batch), block(256);
@@ -699,14 +726,22 @@ extern "C" int attn_fwd_v5(void* stream, const void* q, const void* k,
 
 __global__ __launch_bounds__(256) void attn_delta_kernel(
     const u16* __restrict__ dout, const u16* __restrict__ o,
-    float* __restrict__ delta, long n_rows) {
-  // one 16-lane group per row; 8 elems per thread
-  const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (row >= n_rows) return;
+    float* __restrict__ delta,
+    long do_sb, long do_sh, long do_ss,
+    long o_sb, long o_sh, long o_ss,
+    int n_heads, int S) {
+  // one 16-lane group per row; 8 elems per thread; grid (S/16, H, B)
+  const int s = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int h = blockIdx.y;
+  const int bi = blockIdx.z;
+  if (s >= S) return;
+  const long row = ((long)bi * n_heads + h) * S + s;   // delta is [B,H,S]
   const int e8 = (threadIdx.x & 15) * 8;
   union { uint4 u; u16 h[8]; } a, b;
-  a.u = *reinterpret_cast<const uint4*>(dout + row * ATTN_D + e8);
-  b.u = *reinterpret_cast<const uint4*>(o + row * ATTN_D + e8);
+  a.u = *reinterpret_cast<const uint4*>(
+      dout + (long)bi * do_sb + (long)h * do_sh + (long)s * do_ss + e8);
+  b.u = *reinterpret_cast<const uint4*>(
+      o + (long)bi * o_sb + (long)h * o_sh + (long)s * o_ss + e8);
   float acc = 0.f;
 #pragma unroll
   for (int j = 0; j < 8; ++j)
@@ -736,6 +771,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     long q_sb, long q_sh, long q_ss,
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
+    long do_sb, long do_sh, long do_ss,
+    long dq_sb, long dq_sh, long dq_ss,
     int n_heads, int gqa_group, int S, float scale) {
   // v7-style staging: K rows + V rows by glds into 3-slot rings, K^T
   // built LDS->LDS at tile end, ONE raw barrier per tile, counted vmcnt.
@@ -763,7 +800,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 
   union F8 { bf16x8 v; uint4 u; u16 h[8]; };
   const u16* qptr = q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss;
-  const u16* doptr = dout + (((long)b * n_heads + h) * S + qrow) * ATTN_D;
+  const u16* doptr = dout + (long)b * do_sb + (long)h * do_sh
+                     + (long)qrow * do_ss;
   F8 qf[8], dof[8];
 #pragma unroll
   for (int kc = 0; kc < 8; ++kc) {
@@ -911,7 +949,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     v7_barrier();
   }
 
-  u16* dqrow = dq + (((long)b * n_heads + h) * S + qrow) * ATTN_D;
+  u16* dqrow = dq + (long)b * dq_sb + (long)h * dq_sh + (long)qrow * dq_ss;
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) {
 #pragma unroll
@@ -949,6 +987,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     u16* __restrict__ dv,
     long q_sb, long q_sh, long q_ss,
     long k_sb, long k_sh, long k_ss,
+    long do_sb, long do_sh, long do_ss,
+    long dv_sb, long dv_sh, long dv_ss,
     int n_heads, int n_kv_heads, int S, float scale) {
   const int kvb = blockIdx.x;                // kv block of 256 (asc = heavy 1st)
   const int hkv = blockIdx.y;
@@ -992,7 +1032,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   for (int g = 0; g < gqa_group; ++g) {
     const int h = hkv * gqa_group + g;
     const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
-    const u16* dobase = dout + (((long)b * n_heads + h) * S) * ATTN_D;
+    const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
     const float* lbase = lse + ((long)b * n_heads + h) * S;
 
     // per-thread staging pointers for this head
@@ -1008,11 +1048,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
       qgp[1] = qbase + (long)(qt0 * 64 + r1) * q_ss + in1;
       const int rp2 = (tid >> 4) * 2;
       const int c8 = (tid & 15) * 8;
-      dtp[0] = dobase + (long)(qt0 * 64 + rp2) * ATTN_D + c8;
-      dtp[1] = dobase + (long)(qt0 * 64 + rp2 + 1) * ATTN_D + c8;
+      dtp[0] = dobase + (long)(qt0 * 64 + rp2) * do_ss + c8;
+      dtp[1] = dobase + (long)(qt0 * 64 + rp2 + 1) * do_ss + c8;
     }
     const long qstep = (long)64 * q_ss;
-    const long dostep = (long)64 * ATTN_D;
+    const long dostep = (long)64 * do_ss;
 
 #define BV_STAGE_IN(BUFI, QT)                                               \
     {                                                                       \
@@ -1126,8 +1166,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     }
   }
 
-  // epilogue: dv [B,HKV,S,D] contiguous
-  u16* dvrow = dv + (((long)b * n_kv_heads + hkv) * S + kvrow) * ATTN_D;
+  // epilogue: dv rows through (batch, kv head, row) strides
+  u16* dvrow = dv + (long)b * dv_sb + (long)hkv * dv_sh + (long)kvrow * dv_ss;
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) {
 #pragma unroll
@@ -1169,6 +1209,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     long q_sb, long q_sh, long q_ss,
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
+    long do_sb, long do_sh, long do_ss,
+    long dk_sb, long dk_sh, long dk_ss,
     int n_heads, int n_kv_heads, int S, float scale) {
   const int kvb = blockIdx.x;
   const int hkv = blockIdx.y;
@@ -1216,7 +1258,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   for (int g = 0; g < gqa_group; ++g) {
     const int h = hkv * gqa_group + g;
     const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
-    const u16* dobase = dout + (((long)b * n_heads + h) * S) * ATTN_D;
+    const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
     const float* lbase = lse + ((long)b * n_heads + h) * S;
     const float* dbase = delta + ((long)b * n_heads + h) * S;
 
@@ -1231,15 +1273,15 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
       const int in1 = (((L1 & 255) ^ ((r1 & 15) << 4)) >> 1);
       qgp[0] = qbase + (long)(qt0 * 64 + r0) * q_ss + in0;
       qgp[1] = qbase + (long)(qt0 * 64 + r1) * q_ss + in1;
-      dgp[0] = dobase + (long)(qt0 * 64 + r0) * ATTN_D + in0;
-      dgp[1] = dobase + (long)(qt0 * 64 + r1) * ATTN_D + in1;
+      dgp[0] = dobase + (long)(qt0 * 64 + r0) * do_ss + in0;
+      dgp[1] = dobase + (long)(qt0 * 64 + r1) * do_ss + in1;
       const int rp2 = (tid >> 4) * 2;
       const int c8 = (tid & 15) * 8;
       qtp[0] = qbase + (long)(qt0 * 64 + rp2) * q_ss + c8;
       qtp[1] = qbase + (long)(qt0 * 64 + rp2 + 1) * q_ss + c8;
     }
     const long qstep = (long)64 * q_ss;
-    const long dostep = (long)64 * ATTN_D;
+    const long dostep = (long)64 * do_ss;
 
 #define BK_STAGE_IN(BUFI, QT)                                               \
     {                                                                       \
@@ -1364,7 +1406,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     }
   }
 
-  u16* dkrow = dk + (((long)b * n_kv_heads + hkv) * S + kvrow) * ATTN_D;
+  u16* dkrow = dk + (long)b * dk_sb + (long)hkv * dk_sh + (long)kvrow * dk_ss;
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) {
 #pragma unroll
@@ -1388,6 +1430,63 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 // launchers
 // ---------------------------------------------------------------------------
 
+// batch / head / row strides of one [B, heads, S, 128] operand (elements)
+struct AttnStride { long sb, sh, ss; };
+
+static inline AttnStride attn_dense_stride(int n_heads, int S) {
+  return {(long)n_heads * S * ATTN_D, (long)S * ATTN_D, (long)ATTN_D};
+}
+
+// delta + dq + dv + dk; lse and delta are always dense [B,H,S] fp32
+static int launch_bwd(void* stream, const void* q, const void* k,
+                      const void* v, const void* out, const void* dout,
+                      const void* lse, void* delta,
+                      void* dq, void* dk, void* dv,
+                      AttnStride qs, AttnStride ks, AttnStride vs,
+                      AttnStride os, AttnStride dos,
+                      AttnStride dqs, AttnStride dks, AttnStride dvs,
+                      int batch, int n_heads, int n_kv_heads, int S,
+                      float scale) {
+  if (S <= 0 || S % 256 != 0 || n_heads <= 0 || batch <= 0 ||
+      n_kv_heads <= 0 || n_heads % n_kv_heads != 0)
+    return -1;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(S / 16, n_heads, batch),
+                     dim3(256), 0, st,
+                     (const u16*)dout, (const u16*)out, (float*)delta,
+                     dos.sb, dos.sh, dos.ss, os.sb, os.sh, os.ss,
+                     n_heads, S);
+  {
+    dim3 grid(S / 256, n_heads, batch), block(512);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)v,
+                       (const u16*)dout, (const float*)lse,
+                       (const float*)delta, (u16*)dq,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
+                       dqs.sb, dqs.sh, dqs.ss,
+                       n_heads, n_heads / n_kv_heads, S, scale);
+  }
+  {
+    dim3 grid(S / 256, n_kv_heads, batch), block(512);
+    hipLaunchKernelGGL(attn_bwd_dv_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)dout,
+                       (const float*)lse, (u16*)dv,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
+                       n_heads, n_kv_heads, S, scale);
+    hipLaunchKernelGGL(attn_bwd_dk_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)v,
+                       (const u16*)dout, (const float*)lse,
+                       (const float*)delta, (u16*)dk,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
+                       dks.sb, dks.sh, dks.ss,
+                       n_heads, n_kv_heads, S, scale);
+  }
+  return 0;
+}
+
 extern "C" int attn_bwd(void* stream, const void* q, const void* k,
                         const void* v, const void* out, const void* dout,
                         const void* lse, void* delta,
@@ -1397,40 +1496,32 @@ extern "C" int attn_bwd(void* stream, const void* q, const void* k,
                         long v_sb, long v_sh, long v_ss,
                         int batch, int n_heads, int n_kv_heads, int S,
                         float scale) {
-  if (S <= 0 || S % 256 != 0 || n_heads <= 0 || batch <= 0 ||
-      n_kv_heads <= 0 || n_heads % n_kv_heads != 0)
-    return -1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long n_rows = (long)batch * n_heads * S;
-  hipLaunchKernelGGL(attn_delta_kernel,
-                     dim3((unsigned)((n_rows + 15) / 16)), dim3(256), 0, st,
-                     (const u16*)dout, (const u16*)out, (float*)delta,
-                     n_rows);
-  {
-    dim3 grid(S / 256, n_heads, batch), block(512);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, st,
-                       (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dout, (const float*)lse,
-                       (const float*)delta, (u16*)dq,
-                       q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                       v_sb, v_sh, v_ss, n_heads, n_heads / n_kv_heads, S,
-                       scale);
-  }
-  {
-    dim3 grid(S / 256, n_kv_heads, batch), block(512);
-    hipLaunchKernelGGL(attn_bwd_dv_kernel, grid, block, 0, st,
-                       (const u16*)q, (const u16*)k, (const u16*)dout,
-                       (const float*)lse, (u16*)dv,
-                       q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                       n_heads, n_kv_heads, S, scale);
-    hipLaunchKernelGGL(attn_bwd_dk_kernel, grid, block, 0, st,
-                       (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dout, (const float*)lse,
-                       (const float*)delta, (u16*)dk,
-                       q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                       v_sb, v_sh, v_ss, n_heads, n_kv_heads, S, scale);
-  }
-  return 0;
+  // out, dout, dq: dense [B,H,S,D]; dk, dv: dense [B,HKV,S,D]
+  const AttnStride dh = attn_dense_stride(n_heads, S);
+  const AttnStride dkv = attn_dense_stride(n_kv_heads, S);
+  return launch_bwd(stream, q, k, v, out, dout, lse, delta, dq, dk, dv,
+                    {q_sb, q_sh, q_ss}, {k_sb, k_sh, k_ss},
+                    {v_sb, v_sh, v_ss}, dh, dh, dh, dkv, dkv,
+                    batch, n_heads, n_kv_heads, S, scale);
+}
+
+// attn_bwd with batch/head/row strides for every [.,.,S,128] operand, so
+// the gradients can land in head ranges of one packed [B,S,(H+2HKV)*128]
+// buffer and dout can arrive as [B,S,H*128]. st: 8 stride triples in the
+// order q, k, v, out, dout, dq, dk, dv.
+extern "C" int attn_bwd_strided(void* stream, const void* q, const void* k,
+                                const void* v, const void* out,
+                                const void* dout, const void* lse,
+                                void* delta, void* dq, void* dk, void* dv,
+                                const long* st, int batch, int n_heads,
+                                int n_kv_heads, int S, float scale) {
+  if (!st || !attn_strides_ok(st, 24)) return -1;
+  auto tri = [st](int i) {
+    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
+  };
+  return launch_bwd(stream, q, k, v, out, dout, lse, delta, dq, dk, dv,
+                    tri(0), tri(1), tri(2), tri(3), tri(4), tri(5), tri(6),
+                    tri(7), batch, n_heads, n_kv_heads, S, scale);
 }
 
 // ===========================================================================
@@ -1458,6 +1549,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long q_sb, long q_sh, long q_ss,
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
+    long o_sb, long o_sh, long o_ss,
     int n_heads, int gqa_group, int S, float scale2) {
   constexpr int NT = 512;
   const int qb = gridDim.x - 1 - blockIdx.x;
@@ -1679,7 +1771,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   }
 
   const float inv_l = 1.0f / l_run;
-  u16* orow = out + (((long)b * n_heads + h) * S + qrow) * ATTN_D;
+  u16* orow = out + (long)b * o_sb + (long)h * o_sh + (long)qrow * o_ss;
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) {
 #pragma unroll
@@ -1708,13 +1800,25 @@ extern "C" int attn_fwd_v7(void* stream, const void* q, const void* k,
                            int batch, int n_heads, int n_kv_heads, int S,
                            float scale) {
   if (S <= 0 || S % 256 != 0 || n_heads % n_kv_heads != 0) return -1;
-  dim3 grid(S / 256, n_heads, batch), block(512);
-  const float scale2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(attn_fwd_v7_kernel, grid, block, 0,
-                     reinterpret_cast<hipStream_t>(stream),
-                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
-                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                     v_sb, v_sh, v_ss, n_heads, n_heads / n_kv_heads, S,
-                     scale2);
+  launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
+                k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
+                (long)n_heads * S * ATTN_D, (long)S * ATTN_D, ATTN_D,
+                batch, n_heads, n_kv_heads, S, scale);
+  return 0;
+}
+
+// v7 forward with `out` through batch/head/row strides as well (lse stays
+// dense [B,H,S]); S % 256 == 0 only. st: 4 stride triples q, k, v, out.
+extern "C" int attn_fwd_strided(void* stream, const void* q, const void* k,
+                                const void* v, void* out, void* lse,
+                                const long* st, int batch, int n_heads,
+                                int n_kv_heads, int S, float scale) {
+  if (S <= 0 || S % 256 != 0 || n_heads <= 0 || batch <= 0 ||
+      n_kv_heads <= 0 || n_heads % n_kv_heads != 0)
+    return -1;
+  if (!st || !attn_strides_ok(st, 12)) return -1;
+  launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
+                st[3], st[4], st[5], st[6], st[7], st[8],
+                st[9], st[10], st[11], batch, n_heads, n_kv_heads, S, scale);
   return 0;
 }

@@ -351,6 +351,33 @@ __global__ void rmsnorm_dw_reduce_kernel(float* __restrict__ dw_partial,
 // One bf16x8 vector per thread chunk; angles from inv_freq[HALF] f32.
 // ===========================================================================
 
+// Rotate one vec8 pair (a = dims i0..i0+7, b = the same dims + HALF) at
+// position pos. Shared by rope_kernel and rope_packed_kernel so the two
+// round identically.
+//
+// The two outputs are x1*c - x2*s and x1*s + x2*c with ONE product of each
+// rounded to fp32 and the other fused. Which one is written out here and
+// contraction is off: left to the compiler, the choice moved with the code
+// around the loop (the same expressions inlined into two kernels fused
+// different products, ~1e-5 of the bf16 outputs differed). The form below is
+// the one rope_kernel has always compiled to, so results do not change.
+__device__ __forceinline__ void rope_rotate8(const BF8& a, const BF8& b,
+                                             BF8& oa, BF8& ob,
+                                             const float* inv_freq, int i0,
+                                             int pos, float sign) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float c, s;
+    __sincosf((float)pos * inv_freq[i0 + j], &s, &c);
+    s *= sign;
+    const float x1 = bf2f(a.h[j]), x2 = bf2f(b.h[j]);
+    const float x2s = x2 * s, x2c = x2 * c;
+    oa.h[j] = f2bf(__builtin_fmaf(x1, c, -x2s));
+    ob.h[j] = f2bf(__builtin_fmaf(x1, s, x2c));
+  }
+}
+
 __global__ void rope_kernel(const uint4* __restrict__ x, uint4* __restrict__ out,
                             const float* __restrict__ inv_freq,
                             long total_vec, int vec_per_half, int n_heads,
@@ -372,17 +399,41 @@ __global__ void rope_kernel(const uint4* __restrict__ x, uint4* __restrict__ out
     BF8 a; a.v = x[base + i0 / 8];
     BF8 b; b.v = x[base + (HALF + i0) / 8];
     BF8 oa, ob;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float c, s;
-      __sincosf((float)pos * inv_freq[i0 + j], &s, &c);
-      s *= sign;
-      const float x1 = bf2f(a.h[j]), x2 = bf2f(b.h[j]);
-      oa.h[j] = f2bf(x1 * c - x2 * s);
-      ob.h[j] = f2bf(x1 * s + x2 * c);
-    }
+    rope_rotate8(a, b, oa, ob, inv_freq, i0, pos, sign);
     out[base + i0 / 8] = oa.v;
     out[base + (HALF + i0) / 8] = ob.v;
+  }
+}
+
+// RoPE over the first n_rot heads of every row of a packed
+// [T, n_heads_total * D] buffer (the fused-QKV layout: q heads, then k
+// heads, then v heads, which are not rotated and not touched). x and out
+// carry their own row strides (in vec8 units) and may be the SAME buffer:
+// each thread reads both halves of its pair before it writes either, and no
+// other thread touches those 16 elements — hence no __restrict__ here.
+__global__ void rope_packed_kernel(const uint4* x, uint4* out,
+                                   const float* __restrict__ inv_freq,
+                                   long total_vec, int vec_per_half,
+                                   int n_rot, long x_row_vec,
+                                   long out_row_vec, int S, int D,
+                                   float sign) {
+  const int HALF = D / 2;
+  for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < total_vec;
+       g += gridDim.x * (long)blockDim.x) {
+    const long per_head = vec_per_half;
+    const long head_g = g / per_head;
+    const int i0 = (int)(g % per_head) * 8;
+    const long t = head_g / n_rot;
+    const int h = (int)(head_g % n_rot);
+    const int pos = (int)(t % S);
+    const long xb = t * x_row_vec + (long)h * (D / 8);
+    const long ob_ = t * out_row_vec + (long)h * (D / 8);
+    BF8 a; a.v = x[xb + i0 / 8];
+    BF8 b; b.v = x[xb + (HALF + i0) / 8];
+    BF8 oa, ob;
+    rope_rotate8(a, b, oa, ob, inv_freq, i0, pos, sign);
+    out[ob_ + i0 / 8] = oa.v;
+    out[ob_ + (HALF + i0) / 8] = ob.v;
   }
 }
 
@@ -1466,6 +1517,26 @@ int rope_at_dev(void* stream, const void* x, void* out, const void* inv_freq,
   hipLaunchKernelGGL(rope_kernel, grid, block, 0, STREAM, (const uint4*)x,
                      (uint4*)out, (const float*)inv_freq, total_vec,
                      vec_per_half, n_heads, S, D, sign, 0, (const long*)pos_dev);
+  return 0;
+}
+
+// rotate heads [0, n_rot) of each packed row; x_row / out_row are the row
+// strides in elements (>= n_rot * D, multiples of 8); out may alias x
+int rope_packed(void* stream, const void* x, void* out, const void* inv_freq,
+                long n_tokens, int n_rot, long x_row, long out_row, int S,
+                int D, float sign) {
+  if (D <= 0 || D % 16 != 0 || n_rot <= 0 || S <= 0) return -1;
+  if (x_row % 8 != 0 || out_row % 8 != 0 || x_row < (long)n_rot * D ||
+      out_row < (long)n_rot * D)
+    return -1;
+  if (n_tokens <= 0) return 0;
+  const int vec_per_half = (D / 2) / 8;
+  const long total_vec = n_tokens * (long)n_rot * vec_per_half;
+  dim3 grid(elementwise_grid(total_vec)), block(BLOCK);
+  hipLaunchKernelGGL(rope_packed_kernel, grid, block, 0, STREAM,
+                     (const uint4*)x, (uint4*)out, (const float*)inv_freq,
+                     total_vec, vec_per_half, n_rot, x_row / 8, out_row / 8,
+                     S, D, sign);
   return 0;
 }
 

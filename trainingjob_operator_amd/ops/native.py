@@ -66,6 +66,7 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.rope, [vp, vp, vp, vp, l, i, i, i, f], i)
     _sig(lib.rope_at, [vp, vp, vp, vp, l, i, i, i, f, i], i)
     _sig(lib.rope_at_dev, [vp, vp, vp, vp, l, i, i, i, f, vp], i)
+    _sig(lib.rope_packed, [vp, vp, vp, vp, l, i, l, l, i, i, f], i)
     _sig(lib.gemv_bf16, [vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_swiglu, [vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_moe_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i], i)
@@ -100,6 +101,12 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
                            l, l, l, l, l, l, l, l, l, i, i, i, i, f], i)
     _sig(lib.attn_bwd, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                         l, l, l, l, l, l, l, l, l, i, i, i, i, f], i)
+    # strided entries: stride triples (batch, head, row) as a host long[]
+    # (see stride_array): q, k, v, out | q, k, v, out, dout, dq, dk, dv
+    lp = ctypes.POINTER(ctypes.c_long)
+    _sig(lib.attn_fwd_strided, [vp, vp, vp, vp, vp, vp, lp, i, i, i, i, f], i)
+    _sig(lib.attn_bwd_strided, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                lp, i, i, i, i, f], i)
     _sig(lib.mfma_probe32, [vp, vp, vp, vp])
     assert lib.hipops_arch_check() == 950
     _lib = lib
@@ -112,6 +119,13 @@ def check_rc(rc: int, op: str, detail: str = "") -> None:
         raise RuntimeError(
             f"hipops {op}: unsupported shape ({detail}) — the kernel "
             f"launcher refused to launch (rc={rc})")
+
+
+def stride_array(*triples):
+    """Pack (batch, head, row) stride triples for the *_strided launchers."""
+    flat = [int(x) for t in triples for x in t]
+    assert len(flat) == 3 * len(triples)
+    return (ctypes.c_long * len(flat))(*flat)
 
 
 def available() -> bool:
