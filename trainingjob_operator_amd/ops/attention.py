@@ -15,6 +15,16 @@ emits O + logsumexp at natural-log scale — exactly what
 aten::_scaled_dot_product_flash_attention_backward consumes — so the
 aten backward remains a drop-in fallback (AITJ_ATTN_BWD=aten, and the
 automatic path for S % 256 != 0).
+
+Block ops for context-parallel ring attention (parallel/cp.py; S % 256
+== 0, S_q == S_kv, native GQA): flash_attention_block_fwd/_bwd run the
+v7 forward and the dq/dv/dk kernels with a compile-time causal switch —
+causal=True is the code above, bit for bit; causal=False visits every
+kv tile with no mask, for blocks wholly below the diagonal. The
+backward takes lse and delta as inputs, so the ring passes the merged
+(global) ones; flash_attention_delta exposes the delta kernel;
+attn_merge_ folds one block's (o, lse) into an fp32 running pair.
+ops/reference.py holds fp32 torch twins of all four.
 """
 from __future__ import annotations
 
@@ -307,3 +317,126 @@ def flash_attention_fwd_v5(q, k, v, scale=None):
         B, H, S, scale)
     native.check_rc(rc, "attn_fwd_v5", f"B={B} H={H} S={S}")
     return out, lse
+
+
+# ---------------------------------------------------------------------------
+# Block ops for context-parallel ring attention (parallel/cp.py)
+# ---------------------------------------------------------------------------
+
+def block_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Shapes the native block ops cover: GPU bf16 [B,H,S,128] /
+    [B,HKV,S,128] with S % 256 == 0, H % HKV == 0, unit last stride."""
+    if q.dim() != 4 or k.dim() != 4:
+        return False
+    B, H, S, D = q.shape
+    HKV = k.shape[1]
+    return (q.is_cuda and k.is_cuda and q.dtype == torch.bfloat16
+            and k.dtype == torch.bfloat16 and D == 128 and k.shape[-1] == 128
+            and S % 256 == 0 and k.shape[2] == S and H % HKV == 0
+            and q.stride(-1) == 1 and k.stride(-1) == 1)
+
+
+def _tri(t: torch.Tensor):
+    assert t.stride(-1) == 1, f"last stride must be 1, got {t.stride()}"
+    return (t.stride(0), t.stride(1), t.stride(2))
+
+
+def _block_dims(q, k, v, op):
+    assert block_supported(q, k) and v.shape == k.shape \
+        and v.dtype == q.dtype and v.is_cuda, (
+            f"{op} needs GPU bf16 [B,H,S,128] / [B,HKV,S,128] with "
+            f"S%256==0; got q {tuple(q.shape)} {q.dtype} "
+            f"kv {tuple(k.shape)} {tuple(v.shape)}")
+    B, H, S, _ = q.shape
+    return B, H, k.shape[1], S
+
+
+def flash_attention_block_fwd(q, k, v, causal: bool,
+                              scale: Optional[float] = None):
+    """One S x S attention block (S_q == S_kv): causal=True is the
+    diagonal block of a longer causal problem (bit-identical to the dense
+    forward), causal=False a block wholly below the diagonal. Returns
+    (o bf16 [B,H,S,128], lse fp32 [B,H,S], natural log)."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    B, H, HKV, S = _block_dims(q, k, v, "flash_attention_block_fwd")
+    lib = native.load(require=True)
+    out = torch.empty(B, H, S, 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+    st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(out))
+    rc = lib.attn_block_fwd(
+        native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        out.data_ptr(), lse.data_ptr(), st, B, H, HKV, S, scale,
+        1 if causal else 0)
+    native.check_rc(rc, "attn_block_fwd", f"B={B} H={H} HKV={HKV} S={S}")
+    return out, lse
+
+
+def flash_attention_delta(out: torch.Tensor,
+                          dout: torch.Tensor) -> torch.Tensor:
+    """delta[b,h,s] = sum_d out*dout (fp32 [B,H,S]) from bf16
+    [B,H,S,128] operands — computed once per ring backward from the
+    merged output."""
+    assert (out.is_cuda and out.dtype == torch.bfloat16
+            and dout.dtype == torch.bfloat16 and out.shape == dout.shape
+            and out.dim() == 4 and out.shape[-1] == 128
+            and out.shape[2] % 16 == 0), (out.shape, out.dtype, dout.dtype)
+    B, H, S, _ = out.shape
+    lib = native.load(require=True)
+    delta = torch.empty(B, H, S, dtype=torch.float32, device=out.device)
+    st = native.stride_array(_tri(out), _tri(dout))
+    rc = lib.attn_delta(native.stream_ptr(), out.data_ptr(), dout.data_ptr(),
+                        delta.data_ptr(), st, B, H, S)
+    native.check_rc(rc, "attn_delta", f"B={B} H={H} S={S}")
+    return delta
+
+
+def flash_attention_block_bwd(q, k, v, dout, lse, delta, causal: bool,
+                              scale: Optional[float] = None):
+    """dq [B,H,S,128], dk, dv [B,HKV,S,128] (bf16) of one block. lse and
+    delta (fp32 [B,H,S]) are inputs: the block's own, or the merged
+    global ones when the block is one of several a q row attends to."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    B, H, HKV, S = _block_dims(q, k, v, "flash_attention_block_bwd")
+    assert dout.shape == q.shape and dout.dtype == torch.bfloat16
+    assert lse.shape == (B, H, S) and delta.shape == (B, H, S)
+    assert lse.dtype == torch.float32 and delta.dtype == torch.float32
+    lib = native.load(require=True)
+    if dout.stride(-1) != 1:
+        dout = dout.contiguous()
+    lse, delta = lse.contiguous(), delta.contiguous()
+    dq = torch.empty(B, H, S, 128, dtype=torch.bfloat16, device=q.device)
+    dk = torch.empty(B, HKV, S, 128, dtype=torch.bfloat16, device=q.device)
+    dv = torch.empty(B, HKV, S, 128, dtype=torch.bfloat16, device=q.device)
+    st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(dout),
+                             _tri(dq), _tri(dk), _tri(dv))
+    rc = lib.attn_block_bwd(
+        native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), st,
+        B, H, HKV, S, scale, 1 if causal else 0)
+    native.check_rc(rc, "attn_block_bwd", f"B={B} H={H} HKV={HKV} S={S}")
+    return dq, dk, dv
+
+
+def attn_merge_(o_acc, lse_acc, o_blk, lse_blk) -> None:
+    """In place: fold (o_blk bf16, lse_blk) into the running fp32 pair
+    (o_acc [B,H,S,128], lse_acc [B,H,S]). Start from o=0, lse=-inf."""
+    B, H, S, D = o_acc.shape
+    assert (o_acc.is_cuda and D == 128 and o_acc.dtype == torch.float32
+            and lse_acc.dtype == torch.float32
+            and lse_blk.dtype == torch.float32
+            and o_blk.dtype == torch.bfloat16
+            and o_acc.is_contiguous() and lse_acc.is_contiguous()
+            and o_blk.shape == o_acc.shape
+            and lse_acc.shape == (B, H, S) and lse_blk.shape == (B, H, S)), (
+        o_acc.shape, o_acc.dtype, o_blk.shape, o_blk.dtype, lse_acc.shape,
+        lse_blk.shape)
+    lib = native.load(require=True)
+    lse_blk = lse_blk.contiguous()
+    st = native.stride_array(_tri(o_blk))
+    rc = lib.attn_merge(native.stream_ptr(), o_acc.data_ptr(),
+                        lse_acc.data_ptr(), o_blk.data_ptr(),
+                        lse_blk.data_ptr(), st, B, H, S)
+    native.check_rc(rc, "attn_merge", f"B={B} H={H} S={S}")

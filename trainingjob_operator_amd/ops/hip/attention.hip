@@ -585,6 +585,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
         m_run * 0.6931471805599453f + __logf(l_run);
 }
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ out,
@@ -612,10 +613,11 @@ static void launch_fwd_v7(void* stream, const void* q, const void* k,
                           long v_sb, long v_sh, long v_ss,
                           long o_sb, long o_sh, long o_ss,
                           int batch, int n_heads, int n_kv_heads, int S,
-                          float scale) {
+                          float scale, bool causal = true) {
   const float scale2 = scale * 1.4426950408889634f;   // fold log2(e)
   dim3 grid(S / 256, n_heads, batch), block(512);
-  hipLaunchKernelGGL(attn_fwd_v7_kernel, grid, block, 0,
+  hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<true>
+                            : attn_fwd_v7_kernel<false>, grid, block, 0,
                      reinterpret_cast<hipStream_t>(stream),
                      (const u16*)q, (const u16*)k, (const u16*)v,
                      (u16*)out, (float*)lse, q_sb, q_sh, q_ss,
@@ -763,6 +765,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(
 #define BQ_V_U16 (V6_BN * ATTN_D)                      // V row image
 #define BQ_BUF_U16 (BQ_K_U16 + BQ_KT_U16 + BQ_V_U16)
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, const u16* __restrict__ dout,
@@ -820,7 +823,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 
   const u16* kbase = k + (long)b * k_sb + (long)hkv * k_sh;
   const u16* vbase = v + (long)b * v_sb + (long)hkv * v_sh;
-  const int n_tiles = (qb + 1) * 4;
+  // causal: tiles up to the diagonal; non-causal: every kv tile
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S / V6_BN;
 
   const u16* kgp[2];
   const u16* vgp[2];
@@ -883,8 +887,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     char* kb = reinterpret_cast<char*>(DQ_K(t % V7_RING));
     char* vb = reinterpret_cast<char*>(DQ_VR(t % V7_RING));
     char* ktb = DQ_KT(t & 1);
-    const bool active = kv0 <= q0w + 31;
-    const bool need_mask = kv0 + V6_BN > q0w;
+    const bool active = !CAUSAL || kv0 <= q0w + 31;
+    const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
 
     union PF { bf16x8 v; unsigned u[4]; } pds[4];
     if (active) {
@@ -981,6 +985,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 #define BV_LSE_U16 128                      // 64 f32
 #define BV_BUF_U16 (BV_Q_U16 + BV_DOT_U16 + BV_LSE_U16)
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ dout, const float* __restrict__ lse,
@@ -1024,7 +1029,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) dvacc[ds][r] = 0.f;
 
-  const int qt0 = kvb * 4;                   // first causal q tile
+  const int qt0 = CAUSAL ? kvb * 4 : 0;      // first q tile that sees us
   const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 dtst[2];
@@ -1100,8 +1105,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
       char* dob = qb_ + DOTOFF;
       const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
       // this wave's kv rows need q >= kv0w; skip tiles fully in the past
-      const bool active = qt * 64 + 63 >= kv0w;
-      const bool need_mask = qt * 64 < kv0w + 32;
+      const bool active = !CAUSAL || qt * 64 + 63 >= kv0w;
+      const bool need_mask = CAUSAL && qt * 64 < kv0w + 32;
 
       union PF { bf16x8 v; unsigned u[4]; } pf[4];
       if (active) {
@@ -1201,6 +1206,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #define BK_DLT_U16 128
 #define BK_BUF_U16 (BK_Q_U16 + BK_DO_U16 + BK_QT_U16 + BK_LSE_U16 + BK_DLT_U16)
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, const u16* __restrict__ dout,
@@ -1250,7 +1256,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) dkacc[ds][r] = 0.f;
 
-  const int qt0 = kvb * 4;
+  const int qt0 = CAUSAL ? kvb * 4 : 0;
   const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 qtst[2];
@@ -1338,8 +1344,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
       char* qtb = qb_ + QTOFF;
       const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
       const float* dltt = reinterpret_cast<const float*>(qb_ + DLTOFF);
-      const bool active = qt * 64 + 63 >= kv0w;
-      const bool need_mask = qt * 64 < kv0w + 32;
+      const bool active = !CAUSAL || qt * 64 + 63 >= kv0w;
+      const bool need_mask = CAUSAL && qt * 64 < kv0w + 32;
 
       union PF { bf16x8 v; unsigned u[4]; } pf[4];
       if (active) {
@@ -1437,28 +1443,30 @@ static inline AttnStride attn_dense_stride(int n_heads, int S) {
   return {(long)n_heads * S * ATTN_D, (long)S * ATTN_D, (long)ATTN_D};
 }
 
-// delta + dq + dv + dk; lse and delta are always dense [B,H,S] fp32
-static int launch_bwd(void* stream, const void* q, const void* k,
-                      const void* v, const void* out, const void* dout,
-                      const void* lse, void* delta,
-                      void* dq, void* dk, void* dv,
-                      AttnStride qs, AttnStride ks, AttnStride vs,
-                      AttnStride os, AttnStride dos,
-                      AttnStride dqs, AttnStride dks, AttnStride dvs,
-                      int batch, int n_heads, int n_kv_heads, int S,
-                      float scale) {
-  if (S <= 0 || S % 256 != 0 || n_heads <= 0 || batch <= 0 ||
-      n_kv_heads <= 0 || n_heads % n_kv_heads != 0)
-    return -1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// delta[q] = rowsum(dO[q] * O[q]); delta is always dense [B,H,S] fp32
+static void launch_delta(hipStream_t st, const void* out, const void* dout,
+                         void* delta, AttnStride os, AttnStride dos,
+                         int batch, int n_heads, int S) {
   hipLaunchKernelGGL(attn_delta_kernel, dim3(S / 16, n_heads, batch),
                      dim3(256), 0, st,
                      (const u16*)dout, (const u16*)out, (float*)delta,
                      dos.sb, dos.sh, dos.ss, os.sb, os.sh, os.ss,
                      n_heads, S);
+}
+
+// dq + dv + dk from given lse and delta (dense [B,H,S] fp32)
+template <bool CAUSAL>
+static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
+                            const void* v, const void* dout,
+                            const void* lse, const void* delta,
+                            void* dq, void* dk, void* dv,
+                            AttnStride qs, AttnStride ks, AttnStride vs,
+                            AttnStride dos, AttnStride dqs, AttnStride dks,
+                            AttnStride dvs, int batch, int n_heads,
+                            int n_kv_heads, int S, float scale) {
   {
     dim3 grid(S / 256, n_heads, batch), block(512);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, st,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<CAUSAL>, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dq,
@@ -1469,13 +1477,13 @@ static int launch_bwd(void* stream, const void* q, const void* k,
   }
   {
     dim3 grid(S / 256, n_kv_heads, batch), block(512);
-    hipLaunchKernelGGL(attn_bwd_dv_kernel, grid, block, 0, st,
+    hipLaunchKernelGGL(attn_bwd_dv_kernel<CAUSAL>, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)dout,
                        (const float*)lse, (u16*)dv,
                        qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                        dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
                        n_heads, n_kv_heads, S, scale);
-    hipLaunchKernelGGL(attn_bwd_dk_kernel, grid, block, 0, st,
+    hipLaunchKernelGGL(attn_bwd_dk_kernel<CAUSAL>, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dk,
@@ -1484,6 +1492,30 @@ static int launch_bwd(void* stream, const void* q, const void* k,
                        dks.sb, dks.sh, dks.ss,
                        n_heads, n_kv_heads, S, scale);
   }
+}
+
+static inline bool attn_block_shape_ok(int batch, int n_heads,
+                                       int n_kv_heads, int S) {
+  return S > 0 && S % 256 == 0 && n_heads > 0 && batch > 0 &&
+         n_kv_heads > 0 && n_heads % n_kv_heads == 0;
+}
+
+// delta + dq + dv + dk (causal)
+static int launch_bwd(void* stream, const void* q, const void* k,
+                      const void* v, const void* out, const void* dout,
+                      const void* lse, void* delta,
+                      void* dq, void* dk, void* dv,
+                      AttnStride qs, AttnStride ks, AttnStride vs,
+                      AttnStride os, AttnStride dos,
+                      AttnStride dqs, AttnStride dks, AttnStride dvs,
+                      int batch, int n_heads, int n_kv_heads, int S,
+                      float scale) {
+  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  launch_delta(st, out, dout, delta, os, dos, batch, n_heads, S);
+  launch_bwd_core<true>(st, q, k, v, dout, lse, delta, dq, dk, dv,
+                        qs, ks, vs, dos, dqs, dks, dvs,
+                        batch, n_heads, n_kv_heads, S, scale);
   return 0;
 }
 
@@ -1540,8 +1572,15 @@ extern "C" int attn_bwd_strided(void* stream, const void* q, const void* k,
 //     reuse and publishing the next transposed image. The transpose
 //     itself needs no barrier: every wave stages by glds exactly the
 //     rows it transposes, so its own counted vmcnt covers them.
+//
+// CAUSAL (also on the dq/dv/dk kernels): true is the causal kernel, tiles
+// up to the diagonal, mask on the diagonal band. false compiles the bound,
+// the tile skip and the mask out: every q block visits all S/64 kv tiles
+// (S_q == S_kv == S), for the blocks of ring attention that lie wholly
+// below the diagonal. Pipeline, ring depth, waits and barriers are shared.
 // ===========================================================================
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ out,
@@ -1591,7 +1630,8 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
 
   const u16* kbase = k + (long)b * k_sb + (long)hkv * k_sh;
   const u16* vbase = v + (long)b * v_sb + (long)hkv * v_sh;
-  const int n_tiles = (qb + 1) * 4;
+  // causal: tiles up to the diagonal; non-causal: every kv tile
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S / V6_BN;
 
   // glds source pointers (swizzle-inverted, advanced per issue)
   const u16* kgp[2];
@@ -1658,8 +1698,8 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
 
     char* kb = reinterpret_cast<char*>(LDSK(t % V7_RING));
     char* vtb = LDSVT(t & 1);
-    const bool active = kv0 <= q0w + 31;
-    const bool need_mask = kv0 + V6_BN > q0w;
+    const bool active = !CAUSAL || kv0 <= q0w + 31;
+    const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
 
     f32x16 s0, s1;
     union PF { bf16x8 v; unsigned u[4]; } pa[4];
@@ -1820,5 +1860,142 @@ extern "C" int attn_fwd_strided(void* stream, const void* q, const void* k,
   launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
                 st[3], st[4], st[5], st[6], st[7], st[8],
                 st[9], st[10], st[11], batch, n_heads, n_kv_heads, S, scale);
+  return 0;
+}
+
+// ===========================================================================
+// Block entries for ring (context-parallel) attention: one S x S block of a
+// longer sequence per call, S_q == S_kv == S. causal != 0 is the diagonal
+// block (the kernels above, unchanged); causal == 0 runs the same kernels
+// with the tile bound and the mask compiled out, for blocks that lie wholly
+// below the diagonal. The backward takes lse and delta as INPUTS so the
+// ring can pass the merged (global) statistics: P = 2^(s*scale2 - lse2)
+// then is this block's share of the global softmax, and since the global
+// lse is >= the block's own, P <= 1 with no clamping.
+// Stride triples (batch, head, row) arrive as a host long[] like the
+// *_strided entries; lse and delta stay dense [B,H,S] fp32.
+// ===========================================================================
+
+// st: 4 triples q, k, v, out
+extern "C" int attn_block_fwd(void* stream, const void* q, const void* k,
+                              const void* v, void* out, void* lse,
+                              const long* st, int batch, int n_heads,
+                              int n_kv_heads, int S, float scale,
+                              int causal) {
+  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
+  if (!st || !attn_strides_ok(st, 12)) return -1;
+  launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
+                st[3], st[4], st[5], st[6], st[7], st[8],
+                st[9], st[10], st[11], batch, n_heads, n_kv_heads, S, scale,
+                causal != 0);
+  return 0;
+}
+
+// st: 2 triples out, dout
+extern "C" int attn_delta(void* stream, const void* out, const void* dout,
+                          void* delta, const long* st, int batch,
+                          int n_heads, int S) {
+  if (S <= 0 || S % 16 != 0 || n_heads <= 0 || batch <= 0) return -1;
+  if (!st || !attn_strides_ok(st, 6)) return -1;
+  launch_delta(reinterpret_cast<hipStream_t>(stream), out, dout, delta,
+               {st[0], st[1], st[2]}, {st[3], st[4], st[5]},
+               batch, n_heads, S);
+  return 0;
+}
+
+// st: 7 triples q, k, v, dout, dq, dk, dv
+extern "C" int attn_block_bwd(void* stream, const void* q, const void* k,
+                              const void* v, const void* dout,
+                              const void* lse, const void* delta,
+                              void* dq, void* dk, void* dv,
+                              const long* st, int batch, int n_heads,
+                              int n_kv_heads, int S, float scale,
+                              int causal) {
+  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
+  if (!st || !attn_strides_ok(st, 21)) return -1;
+  auto tri = [st](int i) {
+    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
+  };
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  if (causal)
+    launch_bwd_core<true>(hs, q, k, v, dout, lse, delta, dq, dk, dv,
+                          tri(0), tri(1), tri(2), tri(3), tri(4), tri(5),
+                          tri(6), batch, n_heads, n_kv_heads, S, scale);
+  else
+    launch_bwd_core<false>(hs, q, k, v, dout, lse, delta, dq, dk, dv,
+                           tri(0), tri(1), tri(2), tri(3), tri(4), tri(5),
+                           tri(6), batch, n_heads, n_kv_heads, S, scale);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// attn_merge: fold one block result (o_blk bf16, lse_blk) into the running
+// fp32 accumulator (o_acc, lse_acc), in place:
+//   lse_new = logaddexp(lse_acc, lse_blk)
+//   o_acc   = o_acc * exp(lse_acc - lse_new) + o_blk * exp(lse_blk - lse_new)
+// One 16-lane group per row, 8 elements per lane (one 16-B bf16 load, two
+// 16-B fp32 loads and stores). The group's lane 0 alone reads and writes
+// the row's lse pair and hands the two weights to the other 15 lanes. The
+// weights go through the pair's max, so an accumulator at (0, -inf) takes
+// weight exactly 0 and the block weight exactly 1 (no -inf - -inf).
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void attn_merge_kernel(
+    float* __restrict__ o_acc, float* __restrict__ lse_acc,
+    const u16* __restrict__ o_blk, const float* __restrict__ lse_blk,
+    long ob_sb, long ob_sh, long ob_ss, int n_heads, int S, long n_rows) {
+  const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (row >= n_rows) return;          // whole 16-lane groups leave together
+  const int sub = threadIdx.x & 15;
+  float wa = 0.f, wb = 0.f;
+  if (sub == 0) {
+    const float la = lse_acc[row], lb = lse_blk[row];
+    const float m = fmaxf(la, lb);
+    if (m != -INFINITY) {
+      const float ea = __expf(la - m), eb = __expf(lb - m);
+      const float sum = ea + eb;
+      wa = ea / sum;
+      wb = eb / sum;
+      lse_acc[row] = m + __logf(sum);
+    }
+  }
+  wa = __shfl(wa, 0, 16);
+  wb = __shfl(wb, 0, 16);
+  const long bh = row / S;
+  const int s = (int)(row - bh * S);
+  const long bi = bh / n_heads;
+  const int h = (int)(bh - bi * n_heads);
+  union { uint4 u; u16 h[8]; } ob;
+  ob.u = *reinterpret_cast<const uint4*>(
+      o_blk + bi * ob_sb + (long)h * ob_sh + (long)s * ob_ss + sub * 8);
+  float4* acc = reinterpret_cast<float4*>(o_acc + row * ATTN_D + sub * 8);
+  float4 a0 = acc[0], a1 = acc[1];
+  a0.x = a0.x * wa + bf2f_(ob.h[0]) * wb;
+  a0.y = a0.y * wa + bf2f_(ob.h[1]) * wb;
+  a0.z = a0.z * wa + bf2f_(ob.h[2]) * wb;
+  a0.w = a0.w * wa + bf2f_(ob.h[3]) * wb;
+  a1.x = a1.x * wa + bf2f_(ob.h[4]) * wb;
+  a1.y = a1.y * wa + bf2f_(ob.h[5]) * wb;
+  a1.z = a1.z * wa + bf2f_(ob.h[6]) * wb;
+  a1.w = a1.w * wa + bf2f_(ob.h[7]) * wb;
+  acc[0] = a0;
+  acc[1] = a1;
+}
+
+// o_acc fp32 dense [B,H,S,128]; lse_acc, lse_blk fp32 dense [B,H,S];
+// o_blk bf16 through st: 1 triple (batch, head, row)
+extern "C" int attn_merge(void* stream, void* o_acc, void* lse_acc,
+                          const void* o_blk, const void* lse_blk,
+                          const long* st, int batch, int n_heads, int S) {
+  if (S <= 0 || n_heads <= 0 || batch <= 0) return -1;
+  if (!st || !attn_strides_ok(st, 3)) return -1;
+  const long n_rows = (long)batch * n_heads * S;
+  const long n_blocks = (n_rows + 15) / 16;
+  if (n_blocks > 0x7fffffffL) return -1;
+  hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)n_blocks), dim3(256),
+                     0, reinterpret_cast<hipStream_t>(stream),
+                     (float*)o_acc, (float*)lse_acc, (const u16*)o_blk,
+                     (const float*)lse_blk, st[0], st[1], st[2],
+                     n_heads, S, n_rows);
   return 0;
 }

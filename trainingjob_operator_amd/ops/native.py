@@ -107,6 +107,14 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.attn_fwd_strided, [vp, vp, vp, vp, vp, vp, lp, i, i, i, i, f], i)
     _sig(lib.attn_bwd_strided, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                 lp, i, i, i, i, f], i)
+    # ring-attention block entries (causal flag last); stride triples:
+    # q, k, v, out | out, dout | q, k, v, dout, dq, dk, dv | o_blk
+    _sig(lib.attn_block_fwd, [vp, vp, vp, vp, vp, vp, lp,
+                              i, i, i, i, f, i], i)
+    _sig(lib.attn_delta, [vp, vp, vp, vp, lp, i, i, i], i)
+    _sig(lib.attn_block_bwd, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, lp,
+                              i, i, i, i, f, i], i)
+    _sig(lib.attn_merge, [vp, vp, vp, vp, vp, lp, i, i, i], i)
     _sig(lib.mfma_probe32, [vp, vp, vp, vp])
     assert lib.hipops_arch_check() == 950
     _lib = lib

@@ -114,3 +114,78 @@ def adamw_step(p32: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
     vhat = v / bc2
     p32.add_(-lr * (mhat / (vhat.sqrt() + eps) + weight_decay * p32))
     p_bf16.copy_(p32.to(p_bf16.dtype))
+
+
+# ---------------------------------------------------------------------------
+# Block attention for the context-parallel ring (twins of the native block
+# ops in ops/attention.py): fp32 math, any dtype / head_dim / length.
+# q [B,H,Sq,D]; k, v [B,HKV,Skv,D] with H % HKV == 0.
+# ---------------------------------------------------------------------------
+
+def _expand_kv(x: torch.Tensor, n_heads: int) -> torch.Tensor:
+    g = n_heads // x.shape[1]
+    return x if g == 1 else x.repeat_interleave(g, dim=1)
+
+
+def _block_scores(q, k, causal: bool, scale: float) -> torch.Tensor:
+    s = torch.matmul(q.float(),
+                     _expand_kv(k, q.shape[1]).float().transpose(-1, -2))
+    s = s * scale
+    if causal:
+        mask = torch.ones(s.shape[-2], s.shape[-1], dtype=torch.bool,
+                          device=s.device).triu(1)
+        s = s.masked_fill(mask, float("-inf"))
+    return s
+
+
+def attention_block_fwd(q, k, v, causal: bool, scale: Optional[float] = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One attention block: (o in q.dtype, lse fp32 [B,H,Sq], natural log)."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    s = _block_scores(q, k, causal, scale)
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    o = torch.matmul(p, _expand_kv(v, q.shape[1]).float())
+    return o.to(q.dtype), lse
+
+
+def attention_delta(out: torch.Tensor, dout: torch.Tensor) -> torch.Tensor:
+    """delta[b,h,s] = sum_d out * dout (fp32)."""
+    return (out.float() * dout.float()).sum(dim=-1)
+
+
+def attention_block_bwd(q, k, v, dout, lse, delta, causal: bool,
+                        scale: Optional[float] = None):
+    """dq, dk, dv of one block given lse and delta — the block's own or
+    the merged (global) ones of a longer key range. dk/dv come back at
+    k's head count (summed over each GQA group), all in the input dtypes."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    B, H, Sq, D = q.shape
+    HKV, Skv = k.shape[1], k.shape[2]
+    s = _block_scores(q, k, causal, scale)
+    p = torch.exp(s - lse.float().unsqueeze(-1))
+    do32 = dout.float()
+    dv = torch.matmul(p.transpose(-1, -2), do32)
+    dp = torch.matmul(do32, _expand_kv(v, H).float().transpose(-1, -2))
+    ds = p * (dp - delta.float().unsqueeze(-1)) * scale
+    dq = torch.matmul(ds, _expand_kv(k, H).float())
+    dk = torch.matmul(ds.transpose(-1, -2), q.float())
+    if HKV != H:
+        dk = dk.reshape(B, HKV, H // HKV, Skv, D).sum(dim=2)
+        dv = dv.reshape(B, HKV, H // HKV, Skv, D).sum(dim=2)
+    return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+
+
+def attn_merge_(o_acc: torch.Tensor, lse_acc: torch.Tensor,
+                o_blk: torch.Tensor, lse_blk: torch.Tensor) -> None:
+    """Fold one block (o_blk, lse_blk) into the fp32 running pair in place.
+    An accumulator at (0, -inf) comes out equal to the block."""
+    lse_new = torch.logaddexp(lse_acc, lse_blk.float())
+    # rows where both are -inf: keep weights 0 instead of exp(nan)
+    dead = torch.isinf(lse_new) & (lse_new < 0)
+    wa = torch.exp(lse_acc - lse_new).masked_fill(dead, 0.0).unsqueeze(-1)
+    wb = torch.exp(lse_blk.float() - lse_new).masked_fill(dead, 0.0)
+    o_acc.mul_(wa).add_(o_blk.float() * wb.unsqueeze(-1))
+    lse_acc.copy_(lse_new)

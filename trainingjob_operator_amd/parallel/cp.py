@@ -27,10 +27,31 @@ on norms/residuals only); CP never materializes the full sequence
 anywhere — it is how a context longer than one GPU's activation budget
 trains at all.
 
+Two implementations of the per-block math sit under the same ring
+schedule, chosen by AITJ_CP_ATTN:
+
+  * block (what `auto`, the default, takes when ops.attention.
+    block_supported holds for the local shard: GPU, bf16, D=128,
+    Sb % 256 == 0): every visited block is one call of the native flash
+    kernels — flash_attention_block_fwd (causal on the diagonal block,
+    non-causal below it) giving (o_j, lse_j), folded into an fp32
+    (o, lse) accumulator by attn_merge_; the backward computes delta once
+    from the merged output and calls flash_attention_block_bwd per block
+    with the GLOBAL lse and delta. No [Sb,Sb] tensor exists anywhere, and
+    K/V and the travelling fp32 dK/dV keep their HKV heads (GQA is native
+    in the kernels), so a Llama-3 32:8 hop moves a quarter of the bytes.
+    AITJ_CP_ATTN=block forces this structure everywhere, on the fp32 torch
+    twins in ops/reference.py where the native ops do not apply — that is
+    how the gloo tests reach it on CPU.
+  * legacy (AITJ_CP_ATTN=legacy, and what `auto` falls back to): fp32
+    torch.matmul block math with an explicit [B,H,Sb,Sb] score tensor and
+    GQA expanded before the ring.
+
 Gloo-verified against the unsharded model (loss + every weight gradient)
-in tests/test_cp_gloo.py. Per-block attention math runs in fp32 through
-torch ops; wiring the native MFMA flash kernels under the ring is a
-future-round optimization (ROADMAP.md).
+in tests/test_cp_gloo.py and tests/test_cp_block_gloo.py; the native block
+ops are verified on the GPU in tests/test_block_attention_gpu.py. The
+multi-rank ring over RCCL has not been timed (profiles/
+r04_ring_attention.md measures one rank's work on one GPU).
 
 No reference counterpart: the reference operator has no parallelism at
 all (SURVEY.md §2.3 — replica counts are its only notion of scale).
@@ -38,6 +59,7 @@ all (SURVEY.md §2.3 — replica counts are its only notion of scale).
 from __future__ import annotations
 
 import math
+import os
 from typing import List, Optional
 
 import torch
@@ -89,12 +111,100 @@ def _block_scores(q32: torch.Tensor, kj: torch.Tensor, scale: float,
     return s
 
 
+def _cp_attn_mode() -> str:
+    mode = os.environ.get("AITJ_CP_ATTN", "auto")
+    if mode not in ("auto", "legacy", "block"):
+        raise ValueError(
+            f"AITJ_CP_ATTN={mode!r}: expected auto, legacy or block")
+    return mode
+
+
+def _block_ops(q, k):
+    """(block_fwd, delta, block_bwd, merge_) — the native flash kernels
+    where they apply, their fp32 torch twins elsewhere."""
+    from ..ops import attention as A
+    from ..ops import reference as R
+    if A.block_supported(q, k):
+        return (A.flash_attention_block_fwd, A.flash_attention_delta,
+                A.flash_attention_block_bwd, A.attn_merge_)
+    return (R.attention_block_fwd, R.attention_delta,
+            R.attention_block_bwd, R.attn_merge_)
+
+
+def uses_block_path(q, k) -> bool:
+    """Whether ring_attention(q, k, ...) takes the block-structured ring
+    (k/v at HKV heads) or the legacy one (k/v expanded to H heads)."""
+    mode = _cp_attn_mode()
+    if mode == "legacy":
+        return False
+    if mode == "block":
+        return True
+    from ..ops.attention import block_supported
+    return block_supported(q, k)
+
+
 class _RingAttention(torch.autograd.Function):
-    """Causal ring attention over [B, H, Sb, D] blocks (equal kv heads —
-    the module expands GQA before the ring)."""
+    """Causal ring attention over [B, H, Sb, D] blocks. block=True: the
+    block-structured ring (k/v [B, HKV, Sb, D]); block=False: the legacy
+    fp32 matmul ring (equal kv heads — the module expands GQA first)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, group, scale):
+    def _block_forward(ctx, q, k, v, group, scale):
+        n = _group_size(group)
+        r = dist.get_rank(group) if n > 1 else 0
+        block_fwd, _, _, merge_ = _block_ops(q, k)
+        B, H, Sb, D = q.shape
+        o_acc = torch.zeros(B, H, Sb, D, dtype=torch.float32,
+                            device=q.device)
+        lse_acc = torch.full((B, H, Sb), float("-inf"), dtype=torch.float32,
+                             device=q.device)
+        kj, vj = k, v
+        j = r
+        for t in range(n):
+            if j <= r:
+                o_j, lse_j = block_fwd(q, kj, vj, j == r, scale)
+                merge_(o_acc, lse_acc, o_j, lse_j)
+            if t + 1 < n:
+                kj, vj = _ring_shift([kj, vj], group)
+                j = (j - 1) % n
+        out = o_acc.to(q.dtype)
+        ctx.save_for_backward(q, k, v, out, lse_acc)
+        ctx.group, ctx.scale = group, scale
+        return out
+
+    @staticmethod
+    def _block_backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        group, scale = ctx.group, ctx.scale
+        n = _group_size(group)
+        r = dist.get_rank(group) if n > 1 else 0
+        _, delta_fn, block_bwd, _ = _block_ops(q, k)
+        dout = dout.to(q.dtype)
+        delta = delta_fn(out, dout)           # once, from the merged out
+        dq = torch.zeros(q.shape, dtype=torch.float32, device=q.device)
+        kj, vj = k, v
+        dkj = torch.zeros(k.shape, dtype=torch.float32, device=k.device)
+        dvj = torch.zeros(v.shape, dtype=torch.float32, device=v.device)
+        j = r
+        for t in range(n):
+            if j <= r:
+                dq_b, dk_b, dv_b = block_bwd(q, kj, vj, dout, lse, delta,
+                                             j == r, scale)
+                dq += dq_b
+                dkj += dk_b
+                dvj += dv_b
+            # n shifts total: the (k, dk, dv) triplet arrives back home
+            if n > 1:
+                kj, vj, dkj, dvj = _ring_shift([kj, vj, dkj, dvj], group)
+                j = (j - 1) % n
+        return (dq.to(q.dtype), dkj.to(k.dtype), dvj.to(v.dtype),
+                None, None, None)
+
+    @staticmethod
+    def forward(ctx, q, k, v, group, scale, block=False):
+        ctx.block = block
+        if block:
+            return _RingAttention._block_forward(ctx, q, k, v, group, scale)
         n = _group_size(group)
         r = dist.get_rank(group) if n > 1 else 0
         q32 = q.float()
@@ -124,6 +234,8 @@ class _RingAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        if ctx.block:
+            return _RingAttention._block_backward(ctx, dout)
         q, k, v, out32, lse = ctx.saved_tensors
         group, scale = ctx.group, ctx.scale
         n = _group_size(group)
@@ -149,15 +261,29 @@ class _RingAttention(torch.autograd.Function):
                 kj, vj, dkj, dvj = _ring_shift([kj, vj, dkj, dvj], group)
                 j = (j - 1) % n
         return (dq.to(q.dtype), dkj.to(k.dtype), dvj.to(v.dtype),
-                None, None)
+                None, None, None)
 
 
 def ring_attention(q, k, v, group, scale: Optional[float] = None):
-    """Causal ring attention; q/k/v [B, H, Sb, D] are this rank's
-    sequence block with equal head counts."""
+    """Causal ring attention; q [B, H, Sb, D] and k/v [B, HKV, Sb, D]
+    are this rank's sequence block.
+
+    Head-count contract: when uses_block_path(q, k) holds (AITJ_CP_ATTN=
+    block, or auto with a shard the native block kernels cover) k/v may
+    carry HKV <= H heads with H % HKV == 0; they circulate unexpanded and
+    dk/dv come back at HKV heads. On the legacy path (AITJ_CP_ATTN=legacy,
+    or auto elsewhere) k/v must already be expanded to H heads."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    return _RingAttention.apply(q, k, v, group, scale)
+    block = uses_block_path(q, k)
+    if block:
+        assert q.shape[1] % k.shape[1] == 0 and k.shape == v.shape, (
+            q.shape, k.shape, v.shape)
+    else:
+        assert k.shape[1] == q.shape[1], (
+            f"legacy ring attention needs kv heads expanded to "
+            f"{q.shape[1]}, got {k.shape[1]}")
+    return _RingAttention.apply(q, k, v, group, scale, block)
 
 
 def _rope_offset(x: torch.Tensor, inv_freq: torch.Tensor,
@@ -179,8 +305,9 @@ def _rope_offset(x: torch.Tensor, inv_freq: torch.Tensor,
 
 class CPAttention(nn.Module):
     """Attention over a sequence shard: replicated weights (same layout
-    as models.llama.Attention), rope at global positions, GQA expanded
-    before the ring (every rank needs full kv heads for its block)."""
+    as models.llama.Attention), rope at global positions. K/V enter the
+    block-structured ring at their HKV heads; the legacy ring gets them
+    expanded (it needs full kv heads for its block matmuls)."""
 
     def __init__(self, cfg: LlamaConfig, group=None):
         super().__init__()
@@ -207,7 +334,7 @@ class CPAttention(nn.Module):
         k = _rope_offset(k, inv_freq, pos0).transpose(1, 2)
         v = v.transpose(1, 2)
         G = cfg.num_heads // cfg.num_kv_heads
-        if G > 1:
+        if G > 1 and not uses_block_path(q, k):
             k = k.repeat_interleave(G, dim=1)
             v = v.repeat_interleave(G, dim=1)
         o = ring_attention(q, k, v, self.group)
