@@ -25,6 +25,33 @@ backward takes lse and delta as inputs, so the ring passes the merged
 (global) ones; flash_attention_delta exposes the delta kernel;
 attn_merge_ folds one block's (o, lse) into an fp32 running pair.
 ops/reference.py holds fp32 torch twins of all four.
+
+Scheduling (hip/attention.hip, `attn_sched_block`): the v7 forward and the
+dq/dv/dk kernels launch on a 1-D grid and decode the block id to (row
+block, head, batch). AITJ_ATTN_SCHED=legacy is the former order (row
+blocks fastest, heavy-first only inside one head); balanced (the default)
+is rank-major - every head's heaviest row block first - with each XCD
+class (id % 8) holding equal work and whole kv heads. Results are
+bit-identical between the two; `lib.attn_sched_decode` is the host copy
+of the decode.
+
+Split dK/dV: with AITJ_ATTN_BWD_SPLIT=1, or by the library's measured
+rule with AITJ_ATTN_BWD_SPLIT=auto (GQA and too few kv workgroups to
+balance the causal walk - see `attn_bwd_use_split`), dv and dk run one
+workgroup per (kv block, q head, batch) into an fp32 workspace
+[2,B,H,S,128] and `attn_bwd_reduce_kernel` sums each kv head's group in
+fixed order and rounds once to bf16: deterministic, one rounding per
+output as before, only the fp32 association differs from the unsplit
+walk. That is enough to move a few thousand dk/dv values per layer pass
+by one bf16 step, so a training step no longer reproduces the unsplit
+run bit for bit; unset (or 0) therefore stays on the unsplit walk. The
+wrappers here size the workspace with `lib.attn_bwd_ws_bytes(B, H, HKV,
+S, causal)`, allocate it with torch.empty and call the `_ws` entries
+(`attn_bwd_ws`, `attn_bwd_strided_ws`, `attn_block_bwd_ws`), which launch
+nothing and return nonzero on a missing or short workspace. The entries
+without `_ws` keep their signatures, decide the same way and take a
+stream-ordered transient workspace themselves; they refuse a capturing
+stream. Both variables are read on every call.
 """
 from __future__ import annotations
 
@@ -44,6 +71,19 @@ def _supported(q: torch.Tensor, k: torch.Tensor) -> bool:
             and (S % 256 == 0 or (S % 64 == 0 and HKV == H))
             and q.stride(-1) == 1 and k.stride(-1) == 1
             and H % HKV == 0)
+
+
+def _bwd_workspace(lib, B, H, HKV, S, causal, device):
+    """The fp32 workspace the native backward wants for this call: (tensor
+    or None, data pointer, bytes). Sized by the library's own rule
+    (attn_bwd_ws_bytes, 0 when dv/dk run unsplit) and taken from torch's
+    allocator, which orders it on the current stream and keeps it in the
+    capture pool while a graph records."""
+    nbytes = lib.attn_bwd_ws_bytes(B, H, HKV, S, 1 if causal else 0)
+    if nbytes <= 0:
+        return None, None, 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr(), nbytes
 
 
 def _run_fwd(q, k, v, scale):
@@ -98,15 +138,16 @@ def _native_backward(q, k, v, out, lse, gout, scale):
     dq = torch.empty(B, H, S, D, dtype=torch.bfloat16, device=q.device)
     dk = torch.empty(B, HKV, S, D, dtype=torch.bfloat16, device=q.device)
     dv = torch.empty(B, HKV, S, D, dtype=torch.bfloat16, device=q.device)
-    rc = lib.attn_bwd(
+    ws, ws_ptr, ws_bytes = _bwd_workspace(lib, B, H, HKV, S, True, q.device)
+    rc = lib.attn_bwd_ws(
         native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
         out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
         q.stride(0), q.stride(1), q.stride(2),
         k.stride(0), k.stride(1), k.stride(2),
         v.stride(0), v.stride(1), v.stride(2),
-        B, H, HKV, S, scale)
-    native.check_rc(rc, "attn_bwd", f"B={B} H={H} HKV={HKV} S={S}")
+        B, H, HKV, S, scale, ws_ptr, ws_bytes)
+    native.check_rc(rc, "attn_bwd_ws", f"B={B} H={H} HKV={HKV} S={S}")
     return dq, dk, dv
 
 
@@ -192,15 +233,18 @@ class _PackedRopeAttention(torch.autograd.Function):
         rs, ws, os_ = (_bhsd_strides(R, D, S), _bhsd_strides(W, D, S),
                        _bhsd_strides(H * D, D, S))
         st = native.stride_array(rs, rs, ws, os_, os_, ws, ws, ws)
-        rc = lib.attn_bwd_strided(
+        ws, ws_ptr, ws_bytes = _bwd_workspace(lib, B, H, HKV, S, True,
+                                              qkv.device)
+        rc = lib.attn_bwd_strided_ws(
             native.stream_ptr(), rot.data_ptr(),
             rot.data_ptr() + H * D * esz,
             qkv.data_ptr() + (H + HKV) * D * esz,
             o.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
             dqkv.data_ptr(), dqkv.data_ptr() + H * D * esz,
             dqkv.data_ptr() + (H + HKV) * D * esz,
-            st, B, H, HKV, S, ctx.scale)
-        native.check_rc(rc, "attn_bwd_strided", f"B={B} H={H} HKV={HKV} S={S}")
+            st, B, H, HKV, S, ctx.scale, ws_ptr, ws_bytes)
+        native.check_rc(rc, "attn_bwd_strided_ws",
+                        f"B={B} H={H} HKV={HKV} S={S}")
         _rope_packed(lib, dqkv, dqkv, inv_freq, B * S, H + HKV, W, W, S, D,
                      -1.0)
         return dqkv, None, None, None, None
@@ -411,12 +455,14 @@ def flash_attention_block_bwd(q, k, v, dout, lse, delta, causal: bool,
     dv = torch.empty(B, HKV, S, 128, dtype=torch.bfloat16, device=q.device)
     st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(dout),
                              _tri(dq), _tri(dk), _tri(dv))
-    rc = lib.attn_block_bwd(
+    ws, ws_ptr, ws_bytes = _bwd_workspace(lib, B, H, HKV, S, causal,
+                                          q.device)
+    rc = lib.attn_block_bwd_ws(
         native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
         dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
         dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), st,
-        B, H, HKV, S, scale, 1 if causal else 0)
-    native.check_rc(rc, "attn_block_bwd", f"B={B} H={H} HKV={HKV} S={S}")
+        B, H, HKV, S, scale, 1 if causal else 0, ws_ptr, ws_bytes)
+    native.check_rc(rc, "attn_block_bwd_ws", f"B={B} H={H} HKV={HKV} S={S}")
     return dq, dk, dv
 
 

@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 typedef unsigned short u16;
 typedef unsigned int u32;
@@ -81,6 +83,59 @@ __device__ __forceinline__ int vt_byte(int d, int kv) {
 // P strip swizzle (row length 128 B = 8 slots): XOR with row & 7.
 __device__ __forceinline__ int p_byte(int row, int col_elem) {
   return (row * ATTN_BN * 2 + col_elem * 2) ^ ((row & 7) << 4);
+}
+
+// ---------------------------------------------------------------------------
+// Block-id decode shared by the v7 forward and the dq/dv/dk kernels, which
+// launch on a 1-D grid of n_row_blocks * n_heads * batch workgroups.
+//
+// rank orders the row blocks by work under the causal mask, 0 = heaviest
+// (fwd/dq: q block n-1-rank; dv/dk: kv block rank); one row block of rank r
+// walks n_row_blocks - r units of four 64-row tile steps.
+//
+// LEGACY is the former 3-D grid read x-fastest: id = rank + n * (head +
+// n_heads * batch). Heavy-first holds only inside each (head, batch), and
+// with n % 8 == 0 a block's XCD class (id % 8: blocks dealt round-robin
+// over the 8 XCDs, observed not promised) gets the same ranks for every
+// (head, batch): per-class work 192 .. 80 units around a mean of 136 at
+// n = 16.
+//
+// BALANCED is rank-major: all M = n_heads * batch pairs at rank 0, then
+// all at rank 1, ... so the launch order is heavy-first globally (hence in
+// every class) whoever takes the next block. When M % 8 == 0 the class is
+// (id % M) % 8, and class c takes the contiguous pair range [c*M/8,
+// (c+1)*M/8) of the (batch, head) order: every class holds every rank M/8
+// times (equal work), and the q heads of one kv head, neighbours in that
+// order, share a class - and so one L2 for that head's K/V - whenever
+// n_kv_heads * batch % 8 == 0. Otherwise pairs go in plain order.
+// Both are bijections of [0, n*M) for every n, n_heads, batch >= 1;
+// results never depend on which is used, only speed does.
+// ---------------------------------------------------------------------------
+
+#define ATTN_SCHED_LEGACY 0
+#define ATTN_SCHED_BALANCED 1
+
+struct AttnBlock { int rank, head, batch; };
+
+__host__ __device__ __forceinline__ AttnBlock attn_sched_block(
+    unsigned id, unsigned n_row_blocks, unsigned n_heads, unsigned batch,
+    int sched) {
+  AttnBlock blk;
+  if (sched == ATTN_SCHED_LEGACY) {
+    const unsigned t = id / n_row_blocks;
+    blk.rank = (int)(id - t * n_row_blocks);
+    blk.batch = (int)(t / n_heads);
+    blk.head = (int)(t - (unsigned)blk.batch * n_heads);
+    return blk;
+  }
+  const unsigned M = n_heads * batch;
+  const unsigned r = id / M;
+  const unsigned w = id - r * M;
+  const unsigned p = (M % 8 == 0) ? (w % 8) * (M / 8) + w / 8 : w;
+  blk.rank = (int)r;
+  blk.batch = (int)(p / n_heads);
+  blk.head = (int)(p - (unsigned)blk.batch * n_heads);
+  return blk;
 }
 
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
@@ -594,7 +649,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
     long o_sb, long o_sh, long o_ss,
-    int n_heads, int gqa_group, int S, float scale2);
+    int n_heads, int gqa_group, int S, float scale2, int batch, int sched);
 
 // The kernels move 16-byte vectors along D, so every stride must keep rows
 // 16-byte aligned (a multiple of 8 bf16 elements).
@@ -604,9 +659,42 @@ static inline bool attn_strides_ok(const long* st, int n) {
   return true;
 }
 
+// Schedule of one launch. AITJ_ATTN_SCHED=legacy|balanced forces every
+// kernel to that decode (read on every call, so both can be timed
+// alternately in one process); unset or anything else takes the default.
+static int attn_sched_mode() {
+  const char* e = std::getenv("AITJ_ATTN_SCHED");
+  if (e && std::strcmp(e, "legacy") == 0) return ATTN_SCHED_LEGACY;
+  return ATTN_SCHED_BALANCED;
+}
+
+// Host-callable decode (tests/test_attention_sched_cpu.py). sched: 0 legacy,
+// 1 balanced. Returns nonzero for an id outside the grid.
+extern "C" int attn_sched_decode(int sched, int id, int n_row_blocks,
+                                 int n_heads, int batch, int* rank,
+                                 int* head, int* b) {
+  if (n_row_blocks <= 0 || n_heads <= 0 || batch <= 0 || id < 0 ||
+      (long)id >= (long)n_row_blocks * n_heads * batch ||
+      (sched != ATTN_SCHED_LEGACY && sched != ATTN_SCHED_BALANCED))
+    return -1;
+  const AttnBlock blk = attn_sched_block((unsigned)id, (unsigned)n_row_blocks,
+                                         (unsigned)n_heads, (unsigned)batch,
+                                         sched);
+  *rank = blk.rank;
+  *head = blk.head;
+  *b = blk.batch;
+  return 0;
+}
+
+// 1-D grid of the four scheduled kernels; the launchers refuse shapes
+// whose workgroup count does not fit an int
+static inline bool attn_grid_ok(int S, int n_heads, int batch) {
+  return (long)(S / 256) * n_heads * batch <= 0x7fffffffL;
+}
+
 // v7 launch shared by attn_fwd, attn_fwd_v7 (contiguous [B,H,S,D] out) and
 // attn_fwd_strided (out through batch/head/row strides)
-static void launch_fwd_v7(void* stream, const void* q, const void* k,
+static int launch_fwd_v7(void* stream, const void* q, const void* k,
                           const void* v, void* out, void* lse,
                           long q_sb, long q_sh, long q_ss,
                           long k_sb, long k_sh, long k_ss,
@@ -614,8 +702,9 @@ static void launch_fwd_v7(void* stream, const void* q, const void* k,
                           long o_sb, long o_sh, long o_ss,
                           int batch, int n_heads, int n_kv_heads, int S,
                           float scale, bool causal = true) {
+  if (!attn_grid_ok(S, n_heads, batch)) return -1;
   const float scale2 = scale * 1.4426950408889634f;   // fold log2(e)
-  dim3 grid(S / 256, n_heads, batch), block(512);
+  dim3 grid((S / 256) * n_heads * batch), block(512);
   hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<true>
                             : attn_fwd_v7_kernel<false>, grid, block, 0,
                      reinterpret_cast<hipStream_t>(stream),
@@ -623,7 +712,9 @@ static void launch_fwd_v7(void* stream, const void* q, const void* k,
                      (u16*)out, (float*)lse, q_sb, q_sh, q_ss,
                      k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
                      o_sb, o_sh, o_ss, n_heads,
-                     n_heads / n_kv_heads, S, scale2);
+                     n_heads / n_kv_heads, S, scale2, batch,
+                     attn_sched_mode());
+  return 0;
 }
 
 extern "C" int attn_fwd(void* stream, const void* q, const void* k,
@@ -644,11 +735,10 @@ extern "C" int attn_fwd(void* stream, const void* q, const void* k,
     if (S % 256 == 0) {
       // v7: 3-deep all-glds pipeline, single raw barrier per tile
       // (299 us vs v6's 346 at B1H32S4096; aotriton 425)
-      launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
-                    k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
-                    (long)n_heads * S * ATTN_D, (long)S * ATTN_D, ATTN_D,
-                    batch, n_heads, n_kv_heads, S, scale);
-      return 0;
+      return launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
+                           k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
+                           (long)n_heads * S * ATTN_D, (long)S * ATTN_D,
+                           ATTN_D, batch, n_heads, n_kv_heads, S, scale);
     }
     dim3 grid(S / 128, n_heads, batch), block(256);
     hipLaunchKernelGGL((attn_fwd_v6_kernel<4>), grid, block, 0,
@@ -723,7 +813,8 @@ extern "C" int attn_fwd_v5(void* stream, const void* q, const void* k,
 // cvt_pk_bf16_f32 + permlane32_swap, row-major images use the k_byte
 // swizzle, transposed images the vt_byte image. GQA: dq walks q heads;
 // dkdv owns a kv head and loops the group's q heads, accumulating dK/dV
-// in registers across the loop.
+// in registers across the loop - or, SPLIT, owns one q head and leaves an
+// fp32 partial for attn_bwd_reduce_kernel (see attn_bwd_use_split).
 // ===========================================================================
 
 __global__ __launch_bounds__(256) void attn_delta_kernel(
@@ -776,13 +867,15 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     long v_sb, long v_sh, long v_ss,
     long do_sb, long do_sh, long do_ss,
     long dq_sb, long dq_sh, long dq_ss,
-    int n_heads, int gqa_group, int S, float scale) {
+    int n_heads, int gqa_group, int S, float scale, int batch, int sched) {
   // v7-style staging: K rows + V rows by glds into 3-slot rings, K^T
   // built LDS->LDS at tile end, ONE raw barrier per tile, counted vmcnt.
   constexpr int NT = 512;
-  const int qb = gridDim.x - 1 - blockIdx.x;
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
+  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
+                                         sched);
+  const int qb = S / 256 - 1 - blk.rank;
+  const int h = blk.head;
+  const int b = blk.batch;
   const int hkv = h / gqa_group;
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
@@ -985,7 +1078,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 #define BV_LSE_U16 128                      // 64 f32
 #define BV_BUF_U16 (BV_Q_U16 + BV_DOT_U16 + BV_LSE_U16)
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ dout, const float* __restrict__ lse,
@@ -994,11 +1087,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     long k_sb, long k_sh, long k_ss,
     long do_sb, long do_sh, long do_ss,
     long dv_sb, long dv_sh, long dv_ss,
-    int n_heads, int n_kv_heads, int S, float scale) {
-  const int kvb = blockIdx.x;                // kv block of 256 (asc = heavy 1st)
-  const int hkv = blockIdx.y;
-  const int b = blockIdx.z;
+    int n_heads, int n_kv_heads, int S, float scale,
+    float* __restrict__ ws, int batch, int sched) {
+  // SPLIT: the workgroup owns (kv block, Q head, batch), walks that one
+  // head and leaves its fp32 accumulator in ws [B,H,S,128];
+  // attn_bwd_reduce_kernel sums the group's partials. Otherwise it owns
+  // (kv block, kv head, batch) and loops the group's q heads.
+  const AttnBlock blk = attn_sched_block(
+      blockIdx.x, S / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
+  const int kvb = blk.rank;                  // kv block of 256 (asc = heavy 1st)
   const int gqa_group = n_heads / n_kv_heads;
+  const int hkv = SPLIT ? blk.head / gqa_group : blk.head;
+  const int b = blk.batch;
+  const int g_lo = SPLIT ? blk.head - hkv * gqa_group : 0;
+  const int g_hi = SPLIT ? g_lo + 1 : gqa_group;
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
   const int lane = tid & 63;
@@ -1034,7 +1136,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 dtst[2];
 
-  for (int g = 0; g < gqa_group; ++g) {
+  for (int g = g_lo; g < g_hi; ++g) {
     const int h = hkv * gqa_group + g;
     const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
     const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
@@ -1171,6 +1273,24 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     }
   }
 
+  if (SPLIT) {
+    // fp32 partial of this q head: 4 consecutive d per accumulator quad
+    float* wrow = ws + (((long)b * n_heads + blk.head) * S + kvrow) * ATTN_D;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d0 = 8 * g + 4 * hi + 32 * ds;
+        float4 wv;
+        wv.x = dvacc[ds][4 * g + 0];
+        wv.y = dvacc[ds][4 * g + 1];
+        wv.z = dvacc[ds][4 * g + 2];
+        wv.w = dvacc[ds][4 * g + 3];
+        *reinterpret_cast<float4*>(wrow + d0) = wv;
+      }
+    }
+    return;
+  }
   // epilogue: dv rows through (batch, kv head, row) strides
   u16* dvrow = dv + (long)b * dv_sb + (long)hkv * dv_sh + (long)kvrow * dv_ss;
 #pragma unroll
@@ -1206,7 +1326,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #define BK_DLT_U16 128
 #define BK_BUF_U16 (BK_Q_U16 + BK_DO_U16 + BK_QT_U16 + BK_LSE_U16 + BK_DLT_U16)
 
-template <bool CAUSAL>
+template <bool CAUSAL, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, const u16* __restrict__ dout,
@@ -1217,11 +1337,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     long v_sb, long v_sh, long v_ss,
     long do_sb, long do_sh, long do_ss,
     long dk_sb, long dk_sh, long dk_ss,
-    int n_heads, int n_kv_heads, int S, float scale) {
-  const int kvb = blockIdx.x;
-  const int hkv = blockIdx.y;
-  const int b = blockIdx.z;
+    int n_heads, int n_kv_heads, int S, float scale,
+    float* __restrict__ ws, int batch, int sched) {
+  const AttnBlock blk = attn_sched_block(
+      blockIdx.x, S / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
+  const int kvb = blk.rank;
   const int gqa_group = n_heads / n_kv_heads;
+  const int hkv = SPLIT ? blk.head / gqa_group : blk.head;   // see dv
+  const int b = blk.batch;
+  const int g_lo = SPLIT ? blk.head - hkv * gqa_group : 0;
+  const int g_hi = SPLIT ? g_lo + 1 : gqa_group;
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
   const int lane = tid & 63;
@@ -1261,7 +1386,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 qtst[2];
 
-  for (int g = 0; g < gqa_group; ++g) {
+  for (int g = g_lo; g < g_hi; ++g) {
     const int h = hkv * gqa_group + g;
     const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
     const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
@@ -1412,6 +1537,24 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     }
   }
 
+  if (SPLIT) {
+    // fp32 partial of this q head: 4 consecutive d per accumulator quad
+    float* wrow = ws + (((long)b * n_heads + blk.head) * S + kvrow) * ATTN_D;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d0 = 8 * g + 4 * hi + 32 * ds;
+        float4 wv;
+        wv.x = dkacc[ds][4 * g + 0];
+        wv.y = dkacc[ds][4 * g + 1];
+        wv.z = dkacc[ds][4 * g + 2];
+        wv.w = dkacc[ds][4 * g + 3];
+        *reinterpret_cast<float4*>(wrow + d0) = wv;
+      }
+    }
+    return;
+  }
   u16* dkrow = dk + (long)b * dk_sb + (long)hkv * dk_sh + (long)kvrow * dk_ss;
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) {
@@ -1454,7 +1597,105 @@ static void launch_delta(hipStream_t st, const void* out, const void* dout,
                      n_heads, S);
 }
 
-// dq + dv + dk from given lse and delta (dense [B,H,S] fp32)
+// ---------------------------------------------------------------------------
+// Split dK/dV: sum the gqa_group fp32 partials of each kv head in fixed
+// order ((p0 + p1) + p2) + ..., round once to bf16 (the same
+// v_cvt_pk_bf16_f32 the unsplit epilogue uses) and write dk and dv through
+// their strides. One 16-lane group per (batch, kv head, row), 8 elements
+// per lane; blockIdx.y picks dk (0) or dv (1). No atomics: bit-reproducible.
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void attn_bwd_reduce_kernel(
+    const float* __restrict__ ws_k, const float* __restrict__ ws_v,
+    u16* __restrict__ dk, u16* __restrict__ dv,
+    long dk_sb, long dk_sh, long dk_ss,
+    long dv_sb, long dv_sh, long dv_ss,
+    int n_heads, int n_kv_heads, int S, long n_rows) {
+  const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (row >= n_rows) return;
+  const int sub = threadIdx.x & 15;
+  const int gqa_group = n_heads / n_kv_heads;
+  const long bh = row / S;                    // b * n_kv_heads + hkv
+  const int s = (int)(row - bh * S);
+  const long bi = bh / n_kv_heads;
+  const int hkv = (int)(bh - bi * n_kv_heads);
+  const bool is_v = blockIdx.y != 0;
+  const float* src = (is_v ? ws_v : ws_k)
+      + ((bi * n_heads + (long)hkv * gqa_group) * S + s) * ATTN_D + sub * 8;
+  const long hstep = (long)S * ATTN_D;
+  float4 a0 = reinterpret_cast<const float4*>(src)[0];
+  float4 a1 = reinterpret_cast<const float4*>(src)[1];
+  for (int g = 1; g < gqa_group; ++g) {
+    const float4 p0 = reinterpret_cast<const float4*>(src + g * hstep)[0];
+    const float4 p1 = reinterpret_cast<const float4*>(src + g * hstep)[1];
+    a0.x += p0.x; a0.y += p0.y; a0.z += p0.z; a0.w += p0.w;
+    a1.x += p1.x; a1.y += p1.y; a1.z += p1.z; a1.w += p1.w;
+  }
+  uint4 o;
+  o.x = cvt_pk_bf16(a0.x, a0.y);
+  o.y = cvt_pk_bf16(a0.z, a0.w);
+  o.z = cvt_pk_bf16(a1.x, a1.y);
+  o.w = cvt_pk_bf16(a1.z, a1.w);
+  u16* dst = is_v
+      ? dv + bi * dv_sb + (long)hkv * dv_sh + (long)s * dv_ss
+      : dk + bi * dk_sb + (long)hkv * dk_sh + (long)s * dk_ss;
+  *reinterpret_cast<uint4*>(dst + sub * 8) = o;
+}
+
+static inline bool attn_block_shape_ok(int batch, int n_heads,
+                                       int n_kv_heads, int S) {
+  return S > 0 && S % 256 == 0 && n_heads > 0 && batch > 0 &&
+         n_kv_heads > 0 && n_heads % n_kv_heads == 0 &&
+         attn_grid_ok(S, n_heads, batch);
+}
+
+// Whether dv/dk run split per q head. The one place that decides; read on
+// every call. AITJ_ATTN_BWD_SPLIT: 0 or unset = never, 1 = always, auto =
+// the measured rule below.
+//
+// Unset means unsplit because the split changes the fp32 association of the
+// sum over a kv head's q heads: a few thousand of 8.4M dk/dv values per
+// layer pass land one bf16 step away, and a training step does not
+// reproduce the unsplit run's loss and weights bit for bit (Llama-3-8B,
+// 5 steps: loss 12.462067 against 12.529497). Whoever turns it on chooses
+// that; the default computes exactly what the unsplit kernels compute.
+//
+// auto: at 229-256 VGPRs a CU holds one 512-thread dv/dk workgroup, and an
+// unsplit causal workgroup walks gqa_group * (n - kvb) units, the heaviest
+// 1.9x the mean, so the grid only balances by backfill when it holds more
+// than one workgroup per CU. Splitting multiplies the workgroup count by
+// gqa_group at the price of 2 * B*H*S*128 fp32 written and read once.
+// Measured at H=32 HKV=8 S=4096, dv + dk (+ reduction), us, unsplit ->
+// split (profiles/r05_attention_balance.md):
+//   causal      0.5 wg/CU (B=1) 1384 ->  554    1 wg/CU (B=2) 1568 -> 1085
+//               2 wg/CU   (B=4) 1977 -> 2180    4 wg/CU (B=8) 3722 -> 4459
+//   non-causal  0.5 wg/CU (B=1) 1387 ->  876    1 wg/CU (B=2) 1526 -> 1686
+// So auto splits when the group has more than one head and the unsplit grid
+// has fewer than 2 workgroups per CU (causal) or fewer than one
+// (non-causal: equal work, splitting only helps to fill idle CUs).
+#define ATTN_NUM_CUS 256     // MI355X
+static bool attn_bwd_use_split(int batch, int n_heads, int n_kv_heads, int S,
+                               bool causal) {
+  const char* e = std::getenv("AITJ_ATTN_BWD_SPLIT");
+  if (e && std::strcmp(e, "1") == 0) return true;
+  if (!e || std::strcmp(e, "auto") != 0) return false;
+  if (n_heads == n_kv_heads) return false;
+  const long wgs = (long)batch * n_kv_heads * (S / 256);
+  return wgs < (long)(causal ? 2 : 1) * ATTN_NUM_CUS;
+}
+
+// Bytes of fp32 workspace the backward of this shape needs right now (dk
+// partials [B,H,S,128] then dv partials); 0 = the unsplit path. Host only.
+extern "C" long attn_bwd_ws_bytes(int batch, int n_heads, int n_kv_heads,
+                                  int S, int causal) {
+  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return 0;
+  if (!attn_bwd_use_split(batch, n_heads, n_kv_heads, S, causal != 0))
+    return 0;
+  return 2L * batch * n_heads * S * ATTN_D * (long)sizeof(float);
+}
+
+// dq + dv + dk from given lse and delta (dense [B,H,S] fp32). ws != null
+// selects the split dv/dk (the caller has checked its size).
 template <bool CAUSAL>
 static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                             const void* v, const void* dout,
@@ -1463,9 +1704,11 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                             AttnStride qs, AttnStride ks, AttnStride vs,
                             AttnStride dos, AttnStride dqs, AttnStride dks,
                             AttnStride dvs, int batch, int n_heads,
-                            int n_kv_heads, int S, float scale) {
+                            int n_kv_heads, int S, float scale, void* ws) {
+  const int sched = attn_sched_mode();
+  const int nrb = S / 256;
   {
-    dim3 grid(S / 256, n_heads, batch), block(512);
+    dim3 grid(nrb * n_heads * batch), block(512);
     hipLaunchKernelGGL(attn_bwd_dq_kernel<CAUSAL>, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
@@ -1473,50 +1716,111 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                        vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
                        dqs.sb, dqs.sh, dqs.ss,
-                       n_heads, n_heads / n_kv_heads, S, scale);
+                       n_heads, n_heads / n_kv_heads, S, scale, batch, sched);
   }
-  {
-    dim3 grid(S / 256, n_kv_heads, batch), block(512);
-    hipLaunchKernelGGL(attn_bwd_dv_kernel<CAUSAL>, grid, block, 0, st,
-                       (const u16*)q, (const u16*)k, (const u16*)dout,
-                       (const float*)lse, (u16*)dv,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
-                       n_heads, n_kv_heads, S, scale);
-    hipLaunchKernelGGL(attn_bwd_dk_kernel<CAUSAL>, grid, block, 0, st,
-                       (const u16*)q, (const u16*)k, (const u16*)v,
-                       (const u16*)dout, (const float*)lse,
-                       (const float*)delta, (u16*)dk,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
-                       dks.sb, dks.sh, dks.ss,
-                       n_heads, n_kv_heads, S, scale);
+  const bool split = ws != nullptr;
+  float* ws_k = (float*)ws;
+  float* ws_v = split ? ws_k + (long)batch * n_heads * S * ATTN_D : nullptr;
+  dim3 grid(nrb * (split ? n_heads : n_kv_heads) * batch), block(512);
+  auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
+                         : attn_bwd_dv_kernel<CAUSAL, false>;
+  hipLaunchKernelGGL(dv_kernel, grid, block, 0, st,
+                     (const u16*)q, (const u16*)k, (const u16*)dout,
+                     (const float*)lse, (u16*)dv,
+                     qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                     dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
+                     n_heads, n_kv_heads, S, scale, ws_v, batch, sched);
+  auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
+                         : attn_bwd_dk_kernel<CAUSAL, false>;
+  hipLaunchKernelGGL(dk_kernel, grid, block, 0, st,
+                     (const u16*)q, (const u16*)k, (const u16*)v,
+                     (const u16*)dout, (const float*)lse,
+                     (const float*)delta, (u16*)dk,
+                     qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                     vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
+                     dks.sb, dks.sh, dks.ss,
+                     n_heads, n_kv_heads, S, scale, ws_k, batch, sched);
+  if (split) {
+    const long n_rows = (long)batch * n_kv_heads * S;
+    hipLaunchKernelGGL(attn_bwd_reduce_kernel,
+                       dim3((unsigned)((n_rows + 15) / 16), 2), dim3(256), 0,
+                       st, (const float*)ws_k, (const float*)ws_v,
+                       (u16*)dk, (u16*)dv, dks.sb, dks.sh, dks.ss,
+                       dvs.sb, dvs.sh, dvs.ss, n_heads, n_kv_heads, S,
+                       n_rows);
   }
 }
 
-static inline bool attn_block_shape_ok(int batch, int n_heads,
-                                       int n_kv_heads, int S) {
-  return S > 0 && S % 256 == 0 && n_heads > 0 && batch > 0 &&
-         n_kv_heads > 0 && n_heads % n_kv_heads == 0;
-}
+// everything one backward call needs besides its stream and workspace
+struct AttnBwdArgs {
+  const void *q, *k, *v, *out, *dout, *lse;
+  void *delta, *dq, *dk, *dv;
+  AttnStride qs, ks, vs, os, dos, dqs, dks, dvs;
+  int batch, n_heads, n_kv_heads, S;
+  float scale;
+  bool causal;
+  bool with_delta;     // compute delta from out/dout first (dense entries)
+};
 
-// delta + dq + dv + dk (causal)
-static int launch_bwd(void* stream, const void* q, const void* k,
-                      const void* v, const void* out, const void* dout,
-                      const void* lse, void* delta,
-                      void* dq, void* dk, void* dv,
-                      AttnStride qs, AttnStride ks, AttnStride vs,
-                      AttnStride os, AttnStride dos,
-                      AttnStride dqs, AttnStride dks, AttnStride dvs,
-                      int batch, int n_heads, int n_kv_heads, int S,
-                      float scale) {
-  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  launch_delta(st, out, dout, delta, os, dos, batch, n_heads, S);
-  launch_bwd_core<true>(st, q, k, v, dout, lse, delta, dq, dk, dv,
-                        qs, ks, vs, dos, dqs, dks, dvs,
-                        batch, n_heads, n_kv_heads, S, scale);
+// Launch with the caller's workspace. Nothing is launched unless the
+// workspace covers the path chosen for this call.
+static int launch_bwd_ws(hipStream_t st, const AttnBwdArgs& a, void* ws,
+                         long ws_bytes) {
+  if (!attn_block_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S)) return -1;
+  const long need = attn_bwd_ws_bytes(a.batch, a.n_heads, a.n_kv_heads, a.S,
+                                      a.causal);
+  if (need > 0 && (ws == nullptr || ws_bytes < need)) return -2;
+  if (need == 0) ws = nullptr;
+  if (a.with_delta)
+    launch_delta(st, a.out, a.dout, a.delta, a.os, a.dos, a.batch, a.n_heads,
+                 a.S);
+  if (a.causal)
+    launch_bwd_core<true>(st, a.q, a.k, a.v, a.dout, a.lse, a.delta, a.dq,
+                          a.dk, a.dv, a.qs, a.ks, a.vs, a.dos, a.dqs, a.dks,
+                          a.dvs, a.batch, a.n_heads, a.n_kv_heads, a.S,
+                          a.scale, ws);
+  else
+    launch_bwd_core<false>(st, a.q, a.k, a.v, a.dout, a.lse, a.delta, a.dq,
+                           a.dk, a.dv, a.qs, a.ks, a.vs, a.dos, a.dqs, a.dks,
+                           a.dvs, a.batch, a.n_heads, a.n_kv_heads, a.S,
+                           a.scale, ws);
   return 0;
+}
+
+// The entries without a workspace argument make the same choice and, for
+// the split path, take a transient workspace ordered on the call's stream
+// (stream-ordered allocate, launch, stream-ordered free). That cannot be
+// recorded into a graph, so they refuse a capturing stream: callers that
+// capture use the _ws entries with memory from their own allocator.
+static int launch_bwd_transient(hipStream_t st, const AttnBwdArgs& a) {
+  if (!attn_block_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S)) return -1;
+  const long need = attn_bwd_ws_bytes(a.batch, a.n_heads, a.n_kv_heads, a.S,
+                                      a.causal);
+  if (need == 0) return launch_bwd_ws(st, a, nullptr, 0);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess ||
+      cs != hipStreamCaptureStatusNone)
+    return -3;
+  void* ws = nullptr;
+  if (hipMallocAsync(&ws, (size_t)need, st) != hipSuccess || !ws) return -4;
+  const int rc = launch_bwd_ws(st, a, ws, need);
+  if (hipFreeAsync(ws, st) != hipSuccess) return -5;
+  return rc;
+}
+
+// out, dout, dq: dense [B,H,S,D]; dk, dv: dense [B,HKV,S,D]
+static AttnBwdArgs attn_bwd_dense_args(
+    const void* q, const void* k, const void* v, const void* out,
+    const void* dout, const void* lse, void* delta, void* dq, void* dk,
+    void* dv, long q_sb, long q_sh, long q_ss, long k_sb, long k_sh,
+    long k_ss, long v_sb, long v_sh, long v_ss, int batch, int n_heads,
+    int n_kv_heads, int S, float scale) {
+  const AttnStride dh = attn_dense_stride(n_heads, S);
+  const AttnStride dkv = attn_dense_stride(n_kv_heads, S);
+  return AttnBwdArgs{q, k, v, out, dout, lse, delta, dq, dk, dv,
+                     {q_sb, q_sh, q_ss}, {k_sb, k_sh, k_ss},
+                     {v_sb, v_sh, v_ss}, dh, dh, dh, dkv, dkv,
+                     batch, n_heads, n_kv_heads, S, scale, true, true};
 }
 
 extern "C" int attn_bwd(void* stream, const void* q, const void* k,
@@ -1528,32 +1832,79 @@ extern "C" int attn_bwd(void* stream, const void* q, const void* k,
                         long v_sb, long v_sh, long v_ss,
                         int batch, int n_heads, int n_kv_heads, int S,
                         float scale) {
-  // out, dout, dq: dense [B,H,S,D]; dk, dv: dense [B,HKV,S,D]
-  const AttnStride dh = attn_dense_stride(n_heads, S);
-  const AttnStride dkv = attn_dense_stride(n_kv_heads, S);
-  return launch_bwd(stream, q, k, v, out, dout, lse, delta, dq, dk, dv,
-                    {q_sb, q_sh, q_ss}, {k_sb, k_sh, k_ss},
-                    {v_sb, v_sh, v_ss}, dh, dh, dh, dkv, dkv,
-                    batch, n_heads, n_kv_heads, S, scale);
+  return launch_bwd_transient(
+      reinterpret_cast<hipStream_t>(stream),
+      attn_bwd_dense_args(q, k, v, out, dout, lse, delta, dq, dk, dv,
+                          q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
+                          v_sb, v_sh, v_ss, batch, n_heads, n_kv_heads, S,
+                          scale));
+}
+
+// attn_bwd with the caller's workspace (attn_bwd_ws_bytes; may be null
+// when that is 0)
+extern "C" int attn_bwd_ws(void* stream, const void* q, const void* k,
+                           const void* v, const void* out, const void* dout,
+                           const void* lse, void* delta,
+                           void* dq, void* dk, void* dv,
+                           long q_sb, long q_sh, long q_ss,
+                           long k_sb, long k_sh, long k_ss,
+                           long v_sb, long v_sh, long v_ss,
+                           int batch, int n_heads, int n_kv_heads, int S,
+                           float scale, void* ws, long ws_bytes) {
+  return launch_bwd_ws(
+      reinterpret_cast<hipStream_t>(stream),
+      attn_bwd_dense_args(q, k, v, out, dout, lse, delta, dq, dk, dv,
+                          q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
+                          v_sb, v_sh, v_ss, batch, n_heads, n_kv_heads, S,
+                          scale),
+      ws, ws_bytes);
 }
 
 // attn_bwd with batch/head/row strides for every [.,.,S,128] operand, so
 // the gradients can land in head ranges of one packed [B,S,(H+2HKV)*128]
 // buffer and dout can arrive as [B,S,H*128]. st: 8 stride triples in the
 // order q, k, v, out, dout, dq, dk, dv.
+static bool attn_bwd_strided_args(
+    AttnBwdArgs* a, const void* q, const void* k, const void* v,
+    const void* out, const void* dout, const void* lse, void* delta,
+    void* dq, void* dk, void* dv, const long* st, int batch, int n_heads,
+    int n_kv_heads, int S, float scale) {
+  if (!st || !attn_strides_ok(st, 24)) return false;
+  auto tri = [st](int i) {
+    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
+  };
+  *a = AttnBwdArgs{q, k, v, out, dout, lse, delta, dq, dk, dv,
+                   tri(0), tri(1), tri(2), tri(3), tri(4), tri(5), tri(6),
+                   tri(7), batch, n_heads, n_kv_heads, S, scale, true, true};
+  return true;
+}
+
 extern "C" int attn_bwd_strided(void* stream, const void* q, const void* k,
                                 const void* v, const void* out,
                                 const void* dout, const void* lse,
                                 void* delta, void* dq, void* dk, void* dv,
                                 const long* st, int batch, int n_heads,
                                 int n_kv_heads, int S, float scale) {
-  if (!st || !attn_strides_ok(st, 24)) return -1;
-  auto tri = [st](int i) {
-    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
-  };
-  return launch_bwd(stream, q, k, v, out, dout, lse, delta, dq, dk, dv,
-                    tri(0), tri(1), tri(2), tri(3), tri(4), tri(5), tri(6),
-                    tri(7), batch, n_heads, n_kv_heads, S, scale);
+  AttnBwdArgs a;
+  if (!attn_bwd_strided_args(&a, q, k, v, out, dout, lse, delta, dq, dk, dv,
+                             st, batch, n_heads, n_kv_heads, S, scale))
+    return -1;
+  return launch_bwd_transient(reinterpret_cast<hipStream_t>(stream), a);
+}
+
+extern "C" int attn_bwd_strided_ws(void* stream, const void* q, const void* k,
+                                   const void* v, const void* out,
+                                   const void* dout, const void* lse,
+                                   void* delta, void* dq, void* dk, void* dv,
+                                   const long* st, int batch, int n_heads,
+                                   int n_kv_heads, int S, float scale,
+                                   void* ws, long ws_bytes) {
+  AttnBwdArgs a;
+  if (!attn_bwd_strided_args(&a, q, k, v, out, dout, lse, delta, dq, dk, dv,
+                             st, batch, n_heads, n_kv_heads, S, scale))
+    return -1;
+  return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
+                       ws_bytes);
 }
 
 // ===========================================================================
@@ -1589,11 +1940,13 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
     long o_sb, long o_sh, long o_ss,
-    int n_heads, int gqa_group, int S, float scale2) {
+    int n_heads, int gqa_group, int S, float scale2, int batch, int sched) {
   constexpr int NT = 512;
-  const int qb = gridDim.x - 1 - blockIdx.x;
-  const int h = blockIdx.y;
-  const int b = blockIdx.z;
+  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
+                                         sched);
+  const int qb = S / 256 - 1 - blk.rank;   // longest-running blocks first
+  const int h = blk.head;
+  const int b = blk.batch;
   const int hkv = h / gqa_group;
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
@@ -1840,11 +2193,10 @@ extern "C" int attn_fwd_v7(void* stream, const void* q, const void* k,
                            int batch, int n_heads, int n_kv_heads, int S,
                            float scale) {
   if (S <= 0 || S % 256 != 0 || n_heads % n_kv_heads != 0) return -1;
-  launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
-                k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
-                (long)n_heads * S * ATTN_D, (long)S * ATTN_D, ATTN_D,
-                batch, n_heads, n_kv_heads, S, scale);
-  return 0;
+  return launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
+                       k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
+                       (long)n_heads * S * ATTN_D, (long)S * ATTN_D, ATTN_D,
+                       batch, n_heads, n_kv_heads, S, scale);
 }
 
 // v7 forward with `out` through batch/head/row strides as well (lse stays
@@ -1857,10 +2209,9 @@ extern "C" int attn_fwd_strided(void* stream, const void* q, const void* k,
       n_kv_heads <= 0 || n_heads % n_kv_heads != 0)
     return -1;
   if (!st || !attn_strides_ok(st, 12)) return -1;
-  launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
-                st[3], st[4], st[5], st[6], st[7], st[8],
-                st[9], st[10], st[11], batch, n_heads, n_kv_heads, S, scale);
-  return 0;
+  return launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
+                       st[3], st[4], st[5], st[6], st[7], st[8], st[9],
+                       st[10], st[11], batch, n_heads, n_kv_heads, S, scale);
 }
 
 // ===========================================================================
@@ -1884,11 +2235,10 @@ extern "C" int attn_block_fwd(void* stream, const void* q, const void* k,
                               int causal) {
   if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
   if (!st || !attn_strides_ok(st, 12)) return -1;
-  launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
-                st[3], st[4], st[5], st[6], st[7], st[8],
-                st[9], st[10], st[11], batch, n_heads, n_kv_heads, S, scale,
-                causal != 0);
-  return 0;
+  return launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
+                       st[3], st[4], st[5], st[6], st[7], st[8], st[9],
+                       st[10], st[11], batch, n_heads, n_kv_heads, S, scale,
+                       causal != 0);
 }
 
 // st: 2 triples out, dout
@@ -1904,6 +2254,23 @@ extern "C" int attn_delta(void* stream, const void* out, const void* dout,
 }
 
 // st: 7 triples q, k, v, dout, dq, dk, dv
+static bool attn_block_bwd_args(
+    AttnBwdArgs* a, const void* q, const void* k, const void* v,
+    const void* dout, const void* lse, const void* delta, void* dq, void* dk,
+    void* dv, const long* st, int batch, int n_heads, int n_kv_heads, int S,
+    float scale, int causal) {
+  if (!st || !attn_strides_ok(st, 21)) return false;
+  auto tri = [st](int i) {
+    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
+  };
+  // delta is an input here: never written, no out operand
+  *a = AttnBwdArgs{q, k, v, nullptr, dout, lse, const_cast<void*>(delta),
+                   dq, dk, dv, tri(0), tri(1), tri(2), AttnStride{0, 0, 0},
+                   tri(3), tri(4), tri(5), tri(6), batch, n_heads,
+                   n_kv_heads, S, scale, causal != 0, false};
+  return true;
+}
+
 extern "C" int attn_block_bwd(void* stream, const void* q, const void* k,
                               const void* v, const void* dout,
                               const void* lse, const void* delta,
@@ -1911,21 +2278,26 @@ extern "C" int attn_block_bwd(void* stream, const void* q, const void* k,
                               const long* st, int batch, int n_heads,
                               int n_kv_heads, int S, float scale,
                               int causal) {
-  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
-  if (!st || !attn_strides_ok(st, 21)) return -1;
-  auto tri = [st](int i) {
-    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
-  };
-  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  if (causal)
-    launch_bwd_core<true>(hs, q, k, v, dout, lse, delta, dq, dk, dv,
-                          tri(0), tri(1), tri(2), tri(3), tri(4), tri(5),
-                          tri(6), batch, n_heads, n_kv_heads, S, scale);
-  else
-    launch_bwd_core<false>(hs, q, k, v, dout, lse, delta, dq, dk, dv,
-                           tri(0), tri(1), tri(2), tri(3), tri(4), tri(5),
-                           tri(6), batch, n_heads, n_kv_heads, S, scale);
-  return 0;
+  AttnBwdArgs a;
+  if (!attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                           batch, n_heads, n_kv_heads, S, scale, causal))
+    return -1;
+  return launch_bwd_transient(reinterpret_cast<hipStream_t>(stream), a);
+}
+
+extern "C" int attn_block_bwd_ws(void* stream, const void* q, const void* k,
+                                 const void* v, const void* dout,
+                                 const void* lse, const void* delta,
+                                 void* dq, void* dk, void* dv,
+                                 const long* st, int batch, int n_heads,
+                                 int n_kv_heads, int S, float scale,
+                                 int causal, void* ws, long ws_bytes) {
+  AttnBwdArgs a;
+  if (!attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                           batch, n_heads, n_kv_heads, S, scale, causal))
+    return -1;
+  return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
+                       ws_bytes);
 }
 
 // ---------------------------------------------------------------------------

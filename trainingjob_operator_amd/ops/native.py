@@ -115,6 +115,21 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.attn_block_bwd, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, lp,
                               i, i, i, i, f, i], i)
     _sig(lib.attn_merge, [vp, vp, vp, vp, vp, lp, i, i, i], i)
+    # backward with a caller-owned workspace (ws, ws_bytes last); the size
+    # comes from attn_bwd_ws_bytes(B, H, HKV, S, causal), 0 = none needed
+    _sig(lib.attn_bwd_ws_bytes, [i, i, i, i, i], l)
+    _sig(lib.attn_bwd_ws, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                           l, l, l, l, l, l, l, l, l, i, i, i, i, f,
+                           vp, l], i)
+    _sig(lib.attn_bwd_strided_ws, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   vp, lp, i, i, i, i, f, vp, l], i)
+    _sig(lib.attn_block_bwd_ws, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, lp,
+                                 i, i, i, i, f, i, vp, l], i)
+    # block-id decode of the scheduled attention kernels (host callable):
+    # (sched 0 legacy | 1 balanced, id, row blocks, heads, batch) ->
+    # rank, head, batch
+    ip = ctypes.POINTER(ctypes.c_int)
+    _sig(lib.attn_sched_decode, [i, i, i, i, i, ip, ip, ip], i)
     _sig(lib.mfma_probe32, [vp, vp, vp, vp])
     assert lib.hipops_arch_check() == 950
     _lib = lib
