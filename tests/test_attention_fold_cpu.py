@@ -1,0 +1,115 @@
+"""Strip ownership of the dv/dk workgroups, on the host.
+
+A dv/dk workgroup of rank r has 8 waves, each owning one 32-row kv strip;
+attn_bwd_strips says which, and at which 64-row q tile the workgroup's walk
+starts under the causal mask. It is exported as attn_bwd_strips_decode.
+Identity is the kv block walk (rows rank*256 + wid*32, first tile rank*4);
+the fold pairs half-block r of 128 rows with half-block 2n-1-r so that every
+workgroup does the same causal work. dk and dv are allocated with
+torch.empty, so a strip nobody owns could read back stale but correct on the
+GPU: that every strip has exactly one owner is checked here."""
+import ctypes
+
+import pytest
+
+from trainingjob_operator_amd.ops import native
+
+pytestmark = pytest.mark.skipif(
+    not native.available(), reason="libhipops.so not built")
+
+IDENTITY, FOLD = 0, 1
+ROW_BLOCKS = [1, 2, 3, 8, 16, 17]
+WAVES = 8
+
+
+def _strips(fold, n):
+    """{rank: [(kv0w, qt0) for each wave]}"""
+    lib = native.load(require=True)
+    kv0w, qt0 = ctypes.c_int(), ctypes.c_int()
+    out = {}
+    for rank in range(n):
+        out[rank] = []
+        for wid in range(WAVES):
+            rc = lib.attn_bwd_strips_decode(fold, rank, wid, n,
+                                            ctypes.byref(kv0w),
+                                            ctypes.byref(qt0))
+            assert rc == 0, (fold, rank, wid, n)
+            out[rank].append((kv0w.value, qt0.value))
+    return out
+
+
+def _first_tile(kv0w):
+    """First 64-row q tile the kernels' `qt * 64 + 63 >= kv0w` lets in."""
+    return kv0w // 64
+
+
+def _work(kv0w, n):
+    """q tiles at or after the strip's rows, of 4n in all."""
+    return 4 * n - _first_tile(kv0w)
+
+
+@pytest.mark.parametrize("fold", [IDENTITY, FOLD])
+@pytest.mark.parametrize("n", ROW_BLOCKS)
+def test_every_strip_has_one_owner(fold, n):
+    owned = [kv for waves in _strips(fold, n).values() for kv, _ in waves]
+    assert sorted(owned) == [32 * s for s in range(8 * n)], (fold, n)
+
+
+@pytest.mark.parametrize("n", ROW_BLOCKS)
+def test_identity_is_the_kv_block_walk(n):
+    for rank, waves in _strips(IDENTITY, n).items():
+        assert waves == [(rank * 256 + wid * 32, rank * 4)
+                         for wid in range(WAVES)]
+
+
+def test_fold_of_one_row_block_is_the_identity():
+    assert _strips(FOLD, 1) == _strips(IDENTITY, 1)
+
+
+@pytest.mark.parametrize("n", ROW_BLOCKS)
+def test_fold_gives_every_workgroup_the_same_causal_work(n):
+    per_rank = {rank: sum(_work(kv, n) for kv, _ in waves)
+                for rank, waves in _strips(FOLD, n).items()}
+    assert len(set(per_rank.values())) == 1, per_rank
+    # all tiles of the causal triangle, counted per strip, shared equally
+    total = sum(_work(32 * s, n) for s in range(8 * n))
+    assert per_rank[0] * n == total
+    if n > 1:
+        ident = {rank: sum(_work(kv, n) for kv, _ in waves)
+                 for rank, waves in _strips(IDENTITY, n).items()}
+        assert max(ident.values()) > min(ident.values())
+
+
+@pytest.mark.parametrize("fold", [IDENTITY, FOLD])
+@pytest.mark.parametrize("n", ROW_BLOCKS)
+def test_first_q_tile_is_the_minimum_over_the_waves(fold, n):
+    for rank, waves in _strips(fold, n).items():
+        qt0s = {qt0 for _, qt0 in waves}
+        assert len(qt0s) == 1, (fold, n, rank)            # one per workgroup
+        qt0 = qt0s.pop()
+        assert qt0 == min(_first_tile(kv) for kv, _ in waves), (fold, n, rank)
+        assert 0 <= qt0 < 4 * n
+
+
+def test_fold_pairs_heavy_and_light_waves_four_apart():
+    """Waves w and w+4 hold the strips at the same offset of the heavy and
+    the light half-block."""
+    n = 16
+    for rank, waves in _strips(FOLD, n).items():
+        for w in range(4):
+            assert waves[w][0] == rank * 128 + w * 32
+            assert waves[w + 4][0] == (2 * n - 1 - rank) * 128 + w * 32
+
+
+def test_out_of_range_arguments_are_refused():
+    lib = native.load(require=True)
+    x = ctypes.c_int()
+    p = ctypes.byref(x)
+    assert lib.attn_bwd_strips_decode(FOLD, 0, 0, 16, p, p) == 0
+    assert lib.attn_bwd_strips_decode(FOLD, 16, 0, 16, p, p) != 0
+    assert lib.attn_bwd_strips_decode(FOLD, -1, 0, 16, p, p) != 0
+    assert lib.attn_bwd_strips_decode(FOLD, 0, 8, 16, p, p) != 0
+    assert lib.attn_bwd_strips_decode(FOLD, 0, -1, 16, p, p) != 0
+    assert lib.attn_bwd_strips_decode(FOLD, 0, 0, 0, p, p) != 0
+    assert lib.attn_bwd_strips_decode(2, 0, 0, 16, p, p) != 0
+    assert lib.attn_bwd_strips_decode(-1, 0, 0, 16, p, p) != 0

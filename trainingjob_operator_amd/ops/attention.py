@@ -52,6 +52,17 @@ nothing and return nonzero on a missing or short workspace. The entries
 without `_ws` keep their signatures, decide the same way and take a
 stream-ordered transient workspace themselves; they refuse a capturing
 stream. Both variables are read on every call.
+
+Folded dK/dV strips (`attn_bwd_strips`, `attn_bwd_use_fold`): a causal
+dv/dk workgroup may pair the four 32-row kv strips of half-block i (of
+128 rows) with those of half-block S/128-1-i instead of owning 256
+neighbouring rows, so that every workgroup does the same causal work and
+each SIMD runs one active wave until the walk reaches its light strip.
+Every strip keeps its accumulation order: dk and dv are bit-identical
+either way. AITJ_ATTN_BWD_FOLD=0 never folds, 1 always folds causal
+launches, unset follows the measured rule (fold when the dv/dk grid has at
+most one workgroup per CU - the flagship step does); read on every call.
+`lib.attn_bwd_strips_decode` is the host copy of the ownership function.
 """
 from __future__ import annotations
 

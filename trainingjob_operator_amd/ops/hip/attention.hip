@@ -138,6 +138,47 @@ __host__ __device__ __forceinline__ AttnBlock attn_sched_block(
   return blk;
 }
 
+// ---------------------------------------------------------------------------
+// Which 32-row kv strip a wave of a dv/dk workgroup owns, and the first q
+// tile the workgroup stages (used by the causal kernels only).
+//
+// A strip's result is one wave's chain of MFMA accumulations over (q head,
+// q tile >= its rows, ascending); nothing ties the 8 waves of a workgroup
+// to 8 neighbouring strips. IDENTITY is the kv block walk: workgroup rank
+// owns rows [rank*256, rank*256 + 256) and walks n - rank units, 1 .. n.
+// FOLD cuts the rows into 2n half-blocks of 128 and gives workgroup rank
+// half-block rank (waves 0-3, heavy) and half-block 2n-1-rank (waves 4-7,
+// light): a heavy and a light strip together are active in
+// (4n - 2*rank) + (2*rank + 2) = 4n + 2 tile steps per q head whatever the
+// rank, where two strips of the identity have 8 .. 8n. The walk starts at
+// the heavy half's first tile, 2*rank; the light waves stage and reach the
+// barrier but sit out the tiles before their rows. Every strip still meets
+// the same tiles in the same order, so dk and dv keep their bits.
+// Waves w and w+4 of a 512-thread workgroup share a SIMD (observed, not
+// promised), so a SIMD runs one active wave until the walk reaches its
+// light one. Pairing even with odd waves instead loses most of the gain
+// (profiles/r06_dkdv_fold.md).
+// ---------------------------------------------------------------------------
+
+#define ATTN_STRIPS_IDENTITY 0
+#define ATTN_STRIPS_FOLD 1
+
+struct AttnStrips { int kv0w, qt0; };
+
+__host__ __device__ __forceinline__ AttnStrips attn_bwd_strips(
+    int fold, int rank, int wid, int n_row_blocks) {
+  AttnStrips s;
+  if (fold == ATTN_STRIPS_IDENTITY) {
+    s.kv0w = rank * 256 + wid * 32;
+    s.qt0 = rank * 4;
+    return s;
+  }
+  const int half = wid < 4 ? rank : 2 * n_row_blocks - 1 - rank;
+  s.kv0w = half * 128 + (wid & 3) * 32;
+  s.qt0 = rank * 2;
+  return s;
+}
+
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ out,
@@ -1088,7 +1129,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     long do_sb, long do_sh, long do_ss,
     long dv_sb, long dv_sh, long dv_ss,
     int n_heads, int n_kv_heads, int S, float scale,
-    float* __restrict__ ws, int batch, int sched) {
+    float* __restrict__ ws, int batch, int sched, int fold) {
   // SPLIT: the workgroup owns (kv block, Q head, batch), walks that one
   // head and leaves its fp32 accumulator in ws [B,H,S,128];
   // attn_bwd_reduce_kernel sums the group's partials. Otherwise it owns
@@ -1114,7 +1155,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   const int DOTOFF = BV_Q_U16 * 2;
   const int LSEOFF = (BV_Q_U16 + BV_DOT_U16) * 2;
 
-  const int kv0w = kvb * 256 + wid * 32;
+  // the non-causal walk is equal work already: identity whatever the flag
+  const AttnStrips strips = attn_bwd_strips(
+      CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
+      __builtin_amdgcn_readfirstlane(wid), S / 256);
+  const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;              // this lane's kv row
 
   // K row in registers (persistent across the whole WG lifetime)
@@ -1131,7 +1176,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) dvacc[ds][r] = 0.f;
 
-  const int qt0 = CAUSAL ? kvb * 4 : 0;      // first q tile that sees us
+  const int qt0 = CAUSAL ? strips.qt0 : 0;   // first q tile that sees us
   const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 dtst[2];
@@ -1338,7 +1383,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     long do_sb, long do_sh, long do_ss,
     long dk_sb, long dk_sh, long dk_ss,
     int n_heads, int n_kv_heads, int S, float scale,
-    float* __restrict__ ws, int batch, int sched) {
+    float* __restrict__ ws, int batch, int sched, int fold) {
   const AttnBlock blk = attn_sched_block(
       blockIdx.x, S / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
   const int kvb = blk.rank;
@@ -1362,7 +1407,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   const int LSEOFF = (BK_Q_U16 + BK_DO_U16 + BK_QT_U16) * 2;
   const int DLTOFF = LSEOFF + BK_LSE_U16 * 2;
 
-  const int kv0w = kvb * 256 + wid * 32;
+  const AttnStrips strips = attn_bwd_strips(
+      CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
+      __builtin_amdgcn_readfirstlane(wid), S / 256);   // see dv
+  const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;
 
   union F8 { bf16x8 v; uint4 u; u16 h[8]; };
@@ -1381,7 +1429,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 #pragma unroll
     for (int r = 0; r < 16; ++r) dkacc[ds][r] = 0.f;
 
-  const int qt0 = CAUSAL ? kvb * 4 : 0;
+  const int qt0 = CAUSAL ? strips.qt0 : 0;
   const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 qtst[2];
@@ -1673,6 +1721,9 @@ static inline bool attn_block_shape_ok(int batch, int n_heads,
 // So auto splits when the group has more than one head and the unsplit grid
 // has fewer than 2 workgroups per CU (causal) or fewer than one
 // (non-causal: equal work, splitting only helps to fill idle CUs).
+// Re-measured with the unsplit walk folded (attn_bwd_use_fold): B=1 1147
+// against 491 split, B=2 1203 against 921, B=4 1662 (unfolded) against
+// 1892; the rule stands.
 #define ATTN_NUM_CUS 256     // MI355X
 static bool attn_bwd_use_split(int batch, int n_heads, int n_kv_heads, int S,
                                bool causal) {
@@ -1682,6 +1733,49 @@ static bool attn_bwd_use_split(int batch, int n_heads, int n_kv_heads, int S,
   if (n_heads == n_kv_heads) return false;
   const long wgs = (long)batch * n_kv_heads * (S / 256);
   return wgs < (long)(causal ? 2 : 1) * ATTN_NUM_CUS;
+}
+
+// Whether the causal dv/dk workgroups own folded strips (attn_bwd_strips).
+// The one place that decides; read on every call. AITJ_ATTN_BWD_FOLD: 0 =
+// never, 1 = always (causal); unset or anything else = the measured rule
+// below. The fold changes no bit of dk or dv, so unlike the split the
+// default may use it. Non-causal launches never fold: equal work already.
+//
+// The fold evens out the work of the waves inside one workgroup; a
+// workgroup still walks 4n - 2*rank tile steps per head, the longest as
+// long as the identity's, and gains only where a SIMD runs one active wave
+// instead of two (a tile step then takes 1/1.27 of the time in dv, 1/1.13
+// in dk). With more than one workgroup per CU the identity's heavy-first
+// order already balances by backfill, and the fold, which makes every
+// workgroup long, loses. Measured at H=32 HKV=8 S=4096 causal, dv + dk
+// (+ reduction), us, fold off -> on (profiles/r06_dkdv_fold.md):
+//   unsplit  0.5 wg/CU (B=1) 1336 -> 1147    1 wg/CU (B=2) 1426 -> 1203
+//            2 wg/CU   (B=4) 1662 -> 2066    4 wg/CU (B=8) 3372 -> 4439
+//   split    2 wg/CU   (B=1)  491 ->  576    4 wg/CU (B=2)  921 -> 1136
+//            8 wg/CU   (B=4) 1892 -> 2446   16 wg/CU (B=8) 4235 -> 5369
+// So the rule folds when the dv/dk grid has at most one workgroup per CU.
+// Between 1 and 2 per CU nothing was measured.
+static int attn_bwd_use_fold(int batch, int n_heads, int n_kv_heads, int S,
+                             bool causal, bool split) {
+  if (!causal) return ATTN_STRIPS_IDENTITY;
+  const char* e = std::getenv("AITJ_ATTN_BWD_FOLD");
+  if (e && std::strcmp(e, "0") == 0) return ATTN_STRIPS_IDENTITY;
+  if (e && std::strcmp(e, "1") == 0) return ATTN_STRIPS_FOLD;
+  const long wgs = (long)batch * (split ? n_heads : n_kv_heads) * (S / 256);
+  return wgs <= ATTN_NUM_CUS ? ATTN_STRIPS_FOLD : ATTN_STRIPS_IDENTITY;
+}
+
+// Host-callable strip ownership (tests/test_attention_fold_cpu.py). fold: 0
+// identity, 1 fold. Returns nonzero for arguments outside the launch.
+extern "C" int attn_bwd_strips_decode(int fold, int rank, int wid,
+                                      int n_row_blocks, int* kv0w, int* qt0) {
+  if (n_row_blocks <= 0 || rank < 0 || rank >= n_row_blocks || wid < 0 ||
+      wid >= 8 || (fold != ATTN_STRIPS_IDENTITY && fold != ATTN_STRIPS_FOLD))
+    return -1;
+  const AttnStrips s = attn_bwd_strips(fold, rank, wid, n_row_blocks);
+  *kv0w = s.kv0w;
+  *qt0 = s.qt0;
+  return 0;
 }
 
 // Bytes of fp32 workspace the backward of this shape needs right now (dk
@@ -1721,6 +1815,8 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
   const bool split = ws != nullptr;
   float* ws_k = (float*)ws;
   float* ws_v = split ? ws_k + (long)batch * n_heads * S * ATTN_D : nullptr;
+  const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, CAUSAL,
+                                     split);
   dim3 grid(nrb * (split ? n_heads : n_kv_heads) * batch), block(512);
   auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
                          : attn_bwd_dv_kernel<CAUSAL, false>;
@@ -1729,7 +1825,7 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                      (const float*)lse, (u16*)dv,
                      qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                      dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
-                     n_heads, n_kv_heads, S, scale, ws_v, batch, sched);
+                     n_heads, n_kv_heads, S, scale, ws_v, batch, sched, fold);
   auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
                          : attn_bwd_dk_kernel<CAUSAL, false>;
   hipLaunchKernelGGL(dk_kernel, grid, block, 0, st,
@@ -1739,7 +1835,7 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                      qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                      vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
                      dks.sb, dks.sh, dks.ss,
-                     n_heads, n_kv_heads, S, scale, ws_k, batch, sched);
+                     n_heads, n_kv_heads, S, scale, ws_k, batch, sched, fold);
   if (split) {
     const long n_rows = (long)batch * n_kv_heads * S;
     hipLaunchKernelGGL(attn_bwd_reduce_kernel,

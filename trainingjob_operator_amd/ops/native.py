@@ -130,6 +130,10 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # rank, head, batch
     ip = ctypes.POINTER(ctypes.c_int)
     _sig(lib.attn_sched_decode, [i, i, i, i, i, ip, ip, ip], i)
+    # strip ownership of the dv/dk workgroups (host callable): (fold 0
+    # identity | 1 fold, workgroup rank, wave, row blocks) -> the wave's
+    # first kv row, the workgroup's first q tile
+    _sig(lib.attn_bwd_strips_decode, [i, i, i, i, ip, ip], i)
     _sig(lib.mfma_probe32, [vp, vp, vp, vp])
     assert lib.hipops_arch_check() == 950
     _lib = lib
