@@ -9,6 +9,17 @@ the non-causal forward against the causal one.
 
 usage: ringbench.py [--iters N] [--legacy-iters N] [--legacy-max-gb G]
                     [--totals 8192,32768] [--cps 2,4,8]
+                    [--layout contiguous|zigzag|both] [--rounds N]
+
+With --layout the report is the ring's critical path instead: every virtual
+rank's cp_schedule (parallel/cp.py) is timed step by step, forward (block
+forward + lse merge) and backward (block backward + the fp32 dq/dK/dV
+adds), and each layout gets the sum over ring steps of the SLOWEST rank's
+step: what a compute-then-shift ring waits for. "both" alternates the two
+layouts --rounds times in one process and adds the contiguous/zigzag ratio
+next to the tile-count ratio (cp - 0.5) / (cp / 2); it also times the
+rectangular non-causal forwards against the square one per (row block, kv
+tile) visit.
 
 Communication is not part of it: K/V blocks are local slices.
 """
@@ -26,7 +37,8 @@ import torch.nn.functional as F
 from trainingjob_operator_amd.ops.attention import (
     attn_merge_, flash_attention_block_bwd, flash_attention_block_fwd,
     flash_attention_delta)
-from trainingjob_operator_amd.parallel.cp import _block_scores
+from trainingjob_operator_amd.parallel.cp import (
+    _block_scores, _part, cp_schedule)
 
 B, H, HKV, D = 1, 32, 8, 128
 DEV = "cuda"
@@ -108,6 +120,130 @@ def legacy_fwd_bwd(q, ks, vs, dout, scale):
     return dq.to(q.dtype)
 
 
+def ring_critical_path(S, cp, layout, scale, iters):
+    """Per-step times of every virtual rank under cp_schedule(layout) and
+    the ring's critical path (sum over steps of the slowest rank)."""
+    Sb = S // cp
+    g = torch.Generator(device=DEV).manual_seed(S + cp)
+
+    def rnd(*shape):
+        return (torch.randn(*shape, device=DEV, generator=g) * .5).bfloat16()
+    ks = [rnd(B, HKV, Sb, D) for _ in range(cp)]
+    vs = [rnd(B, HKV, Sb, D) for _ in range(cp)]
+    parts = ("full",) if layout == "contiguous" else ("lo", "hi")
+    rows = Sb // len(parts)
+    fwd = [[0.0] * cp for _ in range(cp)]       # [rank][step] us
+    bwd = [[0.0] * cp for _ in range(cp)]
+    for r in range(cp):
+        q, dout = rnd(B, H, Sb, D), rnd(B, H, Sb, D)
+        sched = cp_schedule(layout, cp, r)
+        acc = [(torch.zeros(B, H, rows, D, dtype=torch.float32, device=DEV),
+                torch.full((B, H, rows), float("-inf"), dtype=torch.float32,
+                           device=DEV)) for _ in parts]
+
+        def fwd_step(j, qp, kvp, causal):
+            o_j, lse_j = flash_attention_block_fwd(
+                _part(q, qp), _part(ks[j], kvp), _part(vs[j], kvp), causal,
+                scale)
+            if qp == "full":
+                for (o_acc, lse_acc), p in zip(acc, parts):
+                    attn_merge_(o_acc, lse_acc, _part(o_j, p),
+                                _part(lse_j, p))
+            else:
+                attn_merge_(acc[1][0], acc[1][1], o_j, lse_j)
+
+        for t, (j, qp, kvp, causal) in enumerate(sched):
+            if qp is not None:
+                fwd[r][t], _ = timed(lambda: fwd_step(j, qp, kvp, causal), 1,
+                                     iters)
+        # the repeated merges only raised lse: P = exp(s - lse) stays <= 1
+        out = torch.cat([a[0] for a in acc], dim=2).to(q.dtype)
+        lse = torch.cat([a[1] for a in acc], dim=2)
+        delta = flash_attention_delta(out, dout)
+        dq = torch.zeros(q.shape, dtype=torch.float32, device=DEV)
+        dkj = torch.zeros(ks[0].shape, dtype=torch.float32, device=DEV)
+        dvj = torch.zeros(vs[0].shape, dtype=torch.float32, device=DEV)
+
+        def bwd_step(j, qp, kvp, causal):
+            dq_b, dk_b, dv_b = flash_attention_block_bwd(
+                _part(q, qp), _part(ks[j], kvp), _part(vs[j], kvp),
+                _part(dout, qp), _part(lse, qp), _part(delta, qp), causal,
+                scale)
+            _part(dq, qp).add_(dq_b)
+            _part(dkj, kvp).add_(dk_b)
+            _part(dvj, kvp).add_(dv_b)
+
+        for t, (j, qp, kvp, causal) in enumerate(sched):
+            if qp is not None:
+                bwd[r][t], _ = timed(lambda: bwd_step(j, qp, kvp, causal), 1,
+                                     iters)
+        del q, dout, acc, out, lse, delta, dq, dkj, dvj
+    crit_f = sum(max(fwd[r][t] for r in range(cp)) for t in range(cp))
+    crit_b = sum(max(bwd[r][t] for r in range(cp)) for t in range(cp))
+    return dict(
+        S=S, cp=cp, Sb=Sb, layout=layout, ring_fwd_us=crit_f,
+        ring_bwd_us=crit_b, ring_fwdbwd_us=crit_f + crit_b,
+        rank_fwd_us=[sum(x) for x in fwd], rank_bwd_us=[sum(x) for x in bwd],
+        slowest_fwd_step_us=[max(fwd[r][t] for r in range(cp))
+                             for t in range(cp)],
+        slowest_bwd_step_us=[max(bwd[r][t] for r in range(cp))
+                             for t in range(cp)])
+
+
+def rect_vs_square(Sb, scale, iters):
+    """Non-causal forward: ns per (row block, kv tile) visit of the square
+    Sb x Sb block and of the two rectangular blocks of a zig-zag step."""
+    g = torch.Generator(device=DEV).manual_seed(Sb)
+
+    def rnd(*shape):
+        return (torch.randn(*shape, device=DEV, generator=g) * .5).bfloat16()
+    q, k, v = rnd(B, H, Sb, D), rnd(B, HKV, Sb, D), rnd(B, HKV, Sb, D)
+    row = dict(Sb=Sb)
+    for name, qp, kvp in (("square", "full", "full"),
+                          ("full_x_lo", "full", "lo"),
+                          ("hi_x_full", "hi", "full")):
+        qq, kk, vv = _part(q, qp), _part(k, kvp), _part(v, kvp)
+        us, _ = timed(lambda: flash_attention_block_fwd(qq, kk, vv, False,
+                                                        scale), 3, iters)
+        visits = B * H * (qq.shape[2] // 256) * (kk.shape[2] // 64)
+        row[f"{name}_fwd_us"] = us
+        row[f"{name}_ns_per_visit"] = us * 1e3 / visits
+    return row
+
+
+def layout_report(args, scale):
+    layouts = (["contiguous", "zigzag"] if args.layout == "both"
+               else [args.layout])
+    seen_sb = set()
+    for S in (int(x) for x in args.totals.split(",")):
+        for cp in (int(x) for x in args.cps.split(",")):
+            got = {}
+            for rnd_i in range(args.rounds):
+                for layout in layouts:          # alternated, one process
+                    row = ring_critical_path(S, cp, layout, scale,
+                                             args.iters)
+                    row["round"] = rnd_i
+                    got.setdefault(layout, []).append(row)
+                    print(json.dumps(row), flush=True)
+                    torch.cuda.empty_cache()
+            if len(layouts) == 2:
+                best = {lay: {k: min(r[k] for r in rows) for k in
+                              ("ring_fwd_us", "ring_bwd_us",
+                               "ring_fwdbwd_us")}
+                        for lay, rows in got.items()}
+                print(json.dumps(dict(
+                    S=S, cp=cp, tile_count_ratio=(cp - 0.5) / (cp / 2),
+                    **{f"{k}_contiguous_over_zigzag":
+                       best["contiguous"][k] / best["zigzag"][k]
+                       for k in best["zigzag"]})), flush=True)
+            Sb = S // cp
+            if "zigzag" in layouts and Sb % 512 == 0 and Sb not in seen_sb:
+                seen_sb.add(Sb)
+                print(json.dumps(rect_vs_square(Sb, scale, args.iters)),
+                      flush=True)
+                torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
@@ -117,9 +253,18 @@ def main():
                          "(~4 live [B,H,Sb,Sb] fp32) exceed this")
     ap.add_argument("--totals", default="8192,32768")
     ap.add_argument("--cps", default="2,4,8")
+    ap.add_argument("--layout", choices=("contiguous", "zigzag", "both"),
+                    default=None,
+                    help="report the ring's critical path per cp layout "
+                         "(see the module docstring) instead of the last "
+                         "rank's block-vs-legacy comparison")
+    ap.add_argument("--rounds", type=int, default=2,
+                    help="with --layout: how often the layouts alternate")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ringbench needs a GPU"
     scale = D ** -0.5
+    if args.layout:
+        return layout_report(args, scale)
     rows = []
     seen_sb = set()
     for S in (int(x) for x in args.totals.split(",")):

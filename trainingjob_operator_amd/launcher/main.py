@@ -183,6 +183,11 @@ def main(argv=None) -> int:
         "AITJ_CP_SIZE", "0")),
                     help="context parallelism: shard the sequence cp-ways "
                          "with ring attention (world = dp x cp)")
+    ap.add_argument("--cp-layout", choices=("contiguous", "zigzag"),
+                    default=os.environ.get("AITJ_CP_LAYOUT", "contiguous"),
+                    help="how --cp shards the sequence: contiguous blocks, "
+                         "or zigzag (rank r holds chunks r and 2cp-1-r of "
+                         "2cp: equal causal work at every ring step)")
     ap.add_argument("--sp", action="store_true",
                     default=os.environ.get("TRAININGJOB_SP", "") == "1",
                     help="sequence parallelism on top of --tp (Megatron "
@@ -253,6 +258,9 @@ def main(argv=None) -> int:
             and not args.zero1, \
             "--cp composes with dp only (tp/pp/ep grids: roadmap)"
         assert args.seq_len % args.cp == 0, "--cp needs seq_len % cp == 0"
+        if args.cp_layout == "zigzag":
+            assert args.seq_len % (2 * args.cp) == 0, \
+                "--cp-layout zigzag needs seq_len % (2*cp) == 0"
     if args.sp:
         assert args.tp > 1, "--sp requires --tp > 1"
         assert args.seq_len % args.tp == 0, "--sp needs seq_len % tp == 0"
@@ -298,7 +306,8 @@ def main(argv=None) -> int:
         import torch
         dev = torch.device(f"cuda:{ctx.local_rank}"
                            if torch.cuda.is_available() else "cpu")
-        trainer = CPTrainer(cfg, cp_size=args.cp, device=dev)
+        trainer = CPTrainer(cfg, cp_size=args.cp, device=dev,
+                            layout=args.cp_layout)
         # weights replicated everywhere: one rank-0 stream, like DP
         ckpt = Checkpointer(args.ckpt_dir)
     elif args.ep:

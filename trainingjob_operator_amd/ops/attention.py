@@ -16,11 +16,16 @@ aten::_scaled_dot_product_flash_attention_backward consumes — so the
 aten backward remains a drop-in fallback (AITJ_ATTN_BWD=aten, and the
 automatic path for S % 256 != 0).
 
-Block ops for context-parallel ring attention (parallel/cp.py; S % 256
-== 0, S_q == S_kv, native GQA): flash_attention_block_fwd/_bwd run the
+Block ops for context-parallel ring attention (parallel/cp.py; lengths
+% 256 == 0, native GQA): flash_attention_block_fwd/_bwd run the
 v7 forward and the dq/dv/dk kernels with a compile-time causal switch —
-causal=True is the code above, bit for bit; causal=False visits every
-kv tile with no mask, for blocks wholly below the diagonal. The
+causal=True is the code above, bit for bit (S_q == S_kv); causal=False
+visits every kv tile with no mask, for blocks wholly below the diagonal,
+and may be rectangular: k.shape[2] != q.shape[2] routes to the rect
+entries (attn_block_fwd_rect, attn_block_bwd_rect_ws; lse/delta
+[B,H,S_q], dk/dv [B,HKV,S_kv,128], workspace by attn_bwd_ws_bytes_rect),
+which the zig-zag ring needs for its half-shard steps. rope_packed_at
+is rope_packed at shard positions (one or two position segments). The
 backward takes lse and delta as inputs, so the ring passes the merged
 (global) ones; flash_attention_delta exposes the delta kernel;
 attn_merge_ folds one block's (o, lse) into an fp32 running pair.
@@ -91,6 +96,16 @@ def _bwd_workspace(lib, B, H, HKV, S, causal, device):
     allocator, which orders it on the current stream and keeps it in the
     capture pool while a graph records."""
     nbytes = lib.attn_bwd_ws_bytes(B, H, HKV, S, 1 if causal else 0)
+    if nbytes <= 0:
+        return None, None, 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr(), nbytes
+
+
+def _bwd_workspace_rect(lib, B, H, HKV, S_q, S_kv, device):
+    """_bwd_workspace for a non-causal S_q x S_kv block
+    (attn_bwd_ws_bytes_rect: the partials are kv rows)."""
+    nbytes = lib.attn_bwd_ws_bytes_rect(B, H, HKV, S_q, S_kv, 0)
     if nbytes <= 0:
         return None, None, 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -194,6 +209,31 @@ def _rope_packed(lib, x, out, inv_freq, n_tokens, n_rot, x_row, out_row,
                          inv_freq.data_ptr(), n_tokens, n_rot, x_row,
                          out_row, S, D, sign)
     native.check_rc(rc, "rope_packed", f"D={D} n_rot={n_rot} row={x_row}")
+
+
+def rope_packed_at(x, out, inv_freq, n_rot, S, seg_len, pos_a, pos_b=0,
+                   sign=1.0, D=128):
+    """RoPE over heads [0, n_rot) of the packed rows of x [B,S,row] into
+    out [B,S,row'] (bf16, contiguous, may be the same tensor) at shard
+    positions: local row s sits at pos_a + s while s < seg_len, then at
+    pos_b + (s - seg_len). S == seg_len is a contiguous shard at offset
+    pos_a, S == 2*seg_len the zig-zag shard; the launcher refuses anything
+    else. Rounds exactly as the dense RoPE kernels do."""
+    assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() \
+        and out.dtype == torch.bfloat16 and out.is_contiguous() \
+        and x.dim() == 3 and out.shape[:2] == x.shape[:2] \
+        and x.shape[1] == S, (x.shape, x.dtype, out.shape, out.dtype, S)
+    assert inv_freq.device == x.device and inv_freq.dtype == torch.float32, (
+        f"inv_freq must be fp32 on {x.device}, got "
+        f"{inv_freq.dtype}@{inv_freq.device}")
+    lib = native.load(require=True)
+    rc = lib.rope_packed_at(native.stream_ptr(), x.data_ptr(), out.data_ptr(),
+                            inv_freq.data_ptr(), x.shape[0] * S, n_rot,
+                            x.shape[2], out.shape[2], S, D, sign, seg_len,
+                            pos_a, pos_b)
+    native.check_rc(rc, "rope_packed_at",
+                    f"D={D} n_rot={n_rot} S={S} seg_len={seg_len} "
+                    f"pos=({pos_a},{pos_b})")
 
 
 class _PackedRopeAttention(torch.autograd.Function):
@@ -379,16 +419,18 @@ def flash_attention_fwd_v5(q, k, v, scale=None):
 # ---------------------------------------------------------------------------
 
 def block_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
-    """Shapes the native block ops cover: GPU bf16 [B,H,S,128] /
-    [B,HKV,S,128] with S % 256 == 0, H % HKV == 0, unit last stride."""
+    """Shapes the native block ops cover: GPU bf16 [B,H,S_q,128] /
+    [B,HKV,S_kv,128] with S_q % 256 == 0 and S_kv % 256 == 0, H % HKV == 0,
+    unit last stride. S_q != S_kv is a rectangular block, non-causal only
+    (the ops themselves refuse causal=True there)."""
     if q.dim() != 4 or k.dim() != 4:
         return False
     B, H, S, D = q.shape
-    HKV = k.shape[1]
+    HKV, Skv = k.shape[1], k.shape[2]
     return (q.is_cuda and k.is_cuda and q.dtype == torch.bfloat16
             and k.dtype == torch.bfloat16 and D == 128 and k.shape[-1] == 128
-            and S % 256 == 0 and k.shape[2] == S and H % HKV == 0
-            and q.stride(-1) == 1 and k.stride(-1) == 1)
+            and S > 0 and S % 256 == 0 and Skv > 0 and Skv % 256 == 0
+            and H % HKV == 0 and q.stride(-1) == 1 and k.stride(-1) == 1)
 
 
 def _tri(t: torch.Tensor):
@@ -396,29 +438,42 @@ def _tri(t: torch.Tensor):
     return (t.stride(0), t.stride(1), t.stride(2))
 
 
-def _block_dims(q, k, v, op):
+def _block_dims(q, k, v, causal, op):
+    """(B, H, HKV, S_q, S_kv) of one block call."""
     assert block_supported(q, k) and v.shape == k.shape \
-        and v.dtype == q.dtype and v.is_cuda, (
-            f"{op} needs GPU bf16 [B,H,S,128] / [B,HKV,S,128] with "
-            f"S%256==0; got q {tuple(q.shape)} {q.dtype} "
+        and v.dtype == q.dtype and v.is_cuda and v.stride(-1) == 1, (
+            f"{op} needs GPU bf16 [B,H,S_q,128] / [B,HKV,S_kv,128] with "
+            f"S_q%256==0 and S_kv%256==0; got q {tuple(q.shape)} {q.dtype} "
             f"kv {tuple(k.shape)} {tuple(v.shape)}")
     B, H, S, _ = q.shape
-    return B, H, k.shape[1], S
+    assert not (causal and k.shape[2] != S), (
+        f"{op}: a causal block is square, got S_q={S} S_kv={k.shape[2]}")
+    return B, H, k.shape[1], S, k.shape[2]
 
 
 def flash_attention_block_fwd(q, k, v, causal: bool,
                               scale: Optional[float] = None):
-    """One S x S attention block (S_q == S_kv): causal=True is the
-    diagonal block of a longer causal problem (bit-identical to the dense
-    forward), causal=False a block wholly below the diagonal. Returns
-    (o bf16 [B,H,S,128], lse fp32 [B,H,S], natural log)."""
+    """One attention block: causal=True is the S x S diagonal block of a
+    longer causal problem (bit-identical to the dense forward), causal=False
+    a block wholly below the diagonal, S_q x S_kv with k.shape[2] != q.shape[2]
+    allowed (the rect entries; a square call takes the square entry as
+    before). Returns (o bf16 [B,H,S_q,128], lse fp32 [B,H,S_q], natural
+    log)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    B, H, HKV, S = _block_dims(q, k, v, "flash_attention_block_fwd")
+    B, H, HKV, S, Skv = _block_dims(q, k, v, causal,
+                                    "flash_attention_block_fwd")
     lib = native.load(require=True)
     out = torch.empty(B, H, S, 128, dtype=torch.bfloat16, device=q.device)
     lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
     st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(out))
+    if Skv != S:
+        rc = lib.attn_block_fwd_rect(
+            native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            out.data_ptr(), lse.data_ptr(), st, B, H, HKV, S, Skv, scale, 0)
+        native.check_rc(rc, "attn_block_fwd_rect",
+                        f"B={B} H={H} HKV={HKV} S_q={S} S_kv={Skv}")
+        return out, lse
     rc = lib.attn_block_fwd(
         native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
         out.data_ptr(), lse.data_ptr(), st, B, H, HKV, S, scale,
@@ -448,12 +503,15 @@ def flash_attention_delta(out: torch.Tensor,
 
 def flash_attention_block_bwd(q, k, v, dout, lse, delta, causal: bool,
                               scale: Optional[float] = None):
-    """dq [B,H,S,128], dk, dv [B,HKV,S,128] (bf16) of one block. lse and
-    delta (fp32 [B,H,S]) are inputs: the block's own, or the merged
-    global ones when the block is one of several a q row attends to."""
+    """dq [B,H,S_q,128], dk, dv [B,HKV,S_kv,128] (bf16) of one block. lse
+    and delta (fp32 [B,H,S_q]) are inputs: the block's own, or the merged
+    global ones when the block is one of several a q row attends to.
+    S_kv != S_q (causal=False only) takes the rect entry and sizes the
+    workspace by its rule."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    B, H, HKV, S = _block_dims(q, k, v, "flash_attention_block_bwd")
+    B, H, HKV, S, Skv = _block_dims(q, k, v, causal,
+                                    "flash_attention_block_bwd")
     assert dout.shape == q.shape and dout.dtype == torch.bfloat16
     assert lse.shape == (B, H, S) and delta.shape == (B, H, S)
     assert lse.dtype == torch.float32 and delta.dtype == torch.float32
@@ -462,10 +520,21 @@ def flash_attention_block_bwd(q, k, v, dout, lse, delta, causal: bool,
         dout = dout.contiguous()
     lse, delta = lse.contiguous(), delta.contiguous()
     dq = torch.empty(B, H, S, 128, dtype=torch.bfloat16, device=q.device)
-    dk = torch.empty(B, HKV, S, 128, dtype=torch.bfloat16, device=q.device)
-    dv = torch.empty(B, HKV, S, 128, dtype=torch.bfloat16, device=q.device)
+    dk = torch.empty(B, HKV, Skv, 128, dtype=torch.bfloat16, device=q.device)
+    dv = torch.empty(B, HKV, Skv, 128, dtype=torch.bfloat16, device=q.device)
     st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(dout),
                              _tri(dq), _tri(dk), _tri(dv))
+    if Skv != S:
+        ws, ws_ptr, ws_bytes = _bwd_workspace_rect(lib, B, H, HKV, S, Skv,
+                                                   q.device)
+        rc = lib.attn_block_bwd_rect_ws(
+            native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+            dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+            dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), st,
+            B, H, HKV, S, Skv, scale, 0, ws_ptr, ws_bytes)
+        native.check_rc(rc, "attn_block_bwd_rect_ws",
+                        f"B={B} H={H} HKV={HKV} S_q={S} S_kv={Skv}")
+        return dq, dk, dv
     ws, ws_ptr, ws_bytes = _bwd_workspace(lib, B, H, HKV, S, causal,
                                           q.device)
     rc = lib.attn_block_bwd_ws(

@@ -690,7 +690,8 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
     long o_sb, long o_sh, long o_ss,
-    int n_heads, int gqa_group, int S, float scale2, int batch, int sched);
+    int n_heads, int gqa_group, int S, float scale2, int batch, int sched,
+    int S_kv);
 
 // The kernels move 16-byte vectors along D, so every stride must keep rows
 // 16-byte aligned (a multiple of 8 bf16 elements).
@@ -742,8 +743,10 @@ static int launch_fwd_v7(void* stream, const void* q, const void* k,
                           long v_sb, long v_sh, long v_ss,
                           long o_sb, long o_sh, long o_ss,
                           int batch, int n_heads, int n_kv_heads, int S,
-                          float scale, bool causal = true) {
-  if (!attn_grid_ok(S, n_heads, batch)) return -1;
+                          float scale, bool causal = true, int S_kv = 0) {
+  // S_kv: k/v rows of a rectangular non-causal block; 0 = square
+  if (S_kv == 0) S_kv = S;
+  if (!attn_grid_ok(S, n_heads, batch) || (causal && S_kv != S)) return -1;
   const float scale2 = scale * 1.4426950408889634f;   // fold log2(e)
   dim3 grid((S / 256) * n_heads * batch), block(512);
   hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<true>
@@ -754,7 +757,7 @@ static int launch_fwd_v7(void* stream, const void* q, const void* k,
                      k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
                      o_sb, o_sh, o_ss, n_heads,
                      n_heads / n_kv_heads, S, scale2, batch,
-                     attn_sched_mode());
+                     attn_sched_mode(), S_kv);
   return 0;
 }
 
@@ -908,7 +911,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     long v_sb, long v_sh, long v_ss,
     long do_sb, long do_sh, long do_ss,
     long dq_sb, long dq_sh, long dq_ss,
-    int n_heads, int gqa_group, int S, float scale, int batch, int sched) {
+    int n_heads, int gqa_group, int S, float scale, int batch, int sched,
+    int S_kv) {
+  // S: q length (row blocks, lse/delta row base); S_kv: k/v length, read by
+  // the non-causal kernel alone (see attn_fwd_v7_kernel).
   // v7-style staging: K rows + V rows by glds into 3-slot rings, K^T
   // built LDS->LDS at tile end, ONE raw barrier per tile, counted vmcnt.
   constexpr int NT = 512;
@@ -958,7 +964,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const u16* kbase = k + (long)b * k_sb + (long)hkv * k_sh;
   const u16* vbase = v + (long)b * v_sb + (long)hkv * v_sh;
   // causal: tiles up to the diagonal; non-causal: every kv tile
-  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S / V6_BN;
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
 
   const u16* kgp[2];
   const u16* vgp[2];
@@ -1129,13 +1135,17 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     long do_sb, long do_sh, long do_ss,
     long dv_sb, long dv_sh, long dv_ss,
     int n_heads, int n_kv_heads, int S, float scale,
-    float* __restrict__ ws, int batch, int sched, int fold) {
+    float* __restrict__ ws, int batch, int sched, int fold, int S_kv_nc) {
+  // S is the q length (q tiles, lse/delta row base). The kv length sets the
+  // row blocks, the strips and the workspace rows; it is S on the causal
+  // path, where the extra argument is never read.
+  const int S_kv = CAUSAL ? S : S_kv_nc;
   // SPLIT: the workgroup owns (kv block, Q head, batch), walks that one
   // head and leaves its fp32 accumulator in ws [B,H,S,128];
   // attn_bwd_reduce_kernel sums the group's partials. Otherwise it owns
   // (kv block, kv head, batch) and loops the group's q heads.
   const AttnBlock blk = attn_sched_block(
-      blockIdx.x, S / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
+      blockIdx.x, S_kv / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
   const int kvb = blk.rank;                  // kv block of 256 (asc = heavy 1st)
   const int gqa_group = n_heads / n_kv_heads;
   const int hkv = SPLIT ? blk.head / gqa_group : blk.head;
@@ -1158,7 +1168,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   // the non-causal walk is equal work already: identity whatever the flag
   const AttnStrips strips = attn_bwd_strips(
       CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
-      __builtin_amdgcn_readfirstlane(wid), S / 256);
+      __builtin_amdgcn_readfirstlane(wid), S_kv / 256);
   const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;              // this lane's kv row
 
@@ -1320,7 +1330,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 
   if (SPLIT) {
     // fp32 partial of this q head: 4 consecutive d per accumulator quad
-    float* wrow = ws + (((long)b * n_heads + blk.head) * S + kvrow) * ATTN_D;
+    float* wrow =
+        ws + (((long)b * n_heads + blk.head) * S_kv + kvrow) * ATTN_D;
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) {
 #pragma unroll
@@ -1383,9 +1394,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     long do_sb, long do_sh, long do_ss,
     long dk_sb, long dk_sh, long dk_ss,
     int n_heads, int n_kv_heads, int S, float scale,
-    float* __restrict__ ws, int batch, int sched, int fold) {
+    float* __restrict__ ws, int batch, int sched, int fold, int S_kv_nc) {
+  // S is the q length (q tiles, lse/delta row base). The kv length sets the
+  // row blocks, the strips and the workspace rows; it is S on the causal
+  // path, where the extra argument is never read.
+  const int S_kv = CAUSAL ? S : S_kv_nc;
   const AttnBlock blk = attn_sched_block(
-      blockIdx.x, S / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
+      blockIdx.x, S_kv / 256, SPLIT ? n_heads : n_kv_heads, batch, sched);
   const int kvb = blk.rank;
   const int gqa_group = n_heads / n_kv_heads;
   const int hkv = SPLIT ? blk.head / gqa_group : blk.head;   // see dv
@@ -1409,7 +1424,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 
   const AttnStrips strips = attn_bwd_strips(
       CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
-      __builtin_amdgcn_readfirstlane(wid), S / 256);   // see dv
+      __builtin_amdgcn_readfirstlane(wid), S_kv / 256);   // see dv
   const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;
 
@@ -1587,7 +1602,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 
   if (SPLIT) {
     // fp32 partial of this q head: 4 consecutive d per accumulator quad
-    float* wrow = ws + (((long)b * n_heads + blk.head) * S + kvrow) * ATTN_D;
+    float* wrow =
+        ws + (((long)b * n_heads + blk.head) * S_kv + kvrow) * ATTN_D;
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) {
 #pragma unroll
@@ -1788,8 +1804,30 @@ extern "C" long attn_bwd_ws_bytes(int batch, int n_heads, int n_kv_heads,
   return 2L * batch * n_heads * S * ATTN_D * (long)sizeof(float);
 }
 
+// A rectangular block: S_q query rows against S_kv key rows, each a multiple
+// of 256. Only non-causal blocks may be rectangular.
+static inline bool attn_rect_shape_ok(int batch, int n_heads, int n_kv_heads,
+                                      int S_q, int S_kv, bool causal) {
+  return attn_block_shape_ok(batch, n_heads, n_kv_heads, S_q) &&
+         attn_block_shape_ok(batch, n_heads, n_kv_heads, S_kv) &&
+         !(causal && S_q != S_kv);
+}
+
+// attn_bwd_ws_bytes for an S_q x S_kv block: the partials are kv rows,
+// dk [B,H,S_kv,128] then dv, and the split rule counts kv workgroups.
+extern "C" long attn_bwd_ws_bytes_rect(int batch, int n_heads, int n_kv_heads,
+                                       int S_q, int S_kv, int causal) {
+  if (!attn_rect_shape_ok(batch, n_heads, n_kv_heads, S_q, S_kv, causal != 0))
+    return 0;
+  if (!attn_bwd_use_split(batch, n_heads, n_kv_heads, S_kv, causal != 0))
+    return 0;
+  return 2L * batch * n_heads * S_kv * ATTN_D * (long)sizeof(float);
+}
+
 // dq + dv + dk from given lse and delta (dense [B,H,S] fp32). ws != null
-// selects the split dv/dk (the caller has checked its size).
+// selects the split dv/dk (the caller has checked its size). S is the q
+// length and sizes the dq grid; S_kv (== S when CAUSAL) sizes the dv/dk
+// grids, the workspace halves and the reduction.
 template <bool CAUSAL>
 static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                             const void* v, const void* dout,
@@ -1798,11 +1836,11 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                             AttnStride qs, AttnStride ks, AttnStride vs,
                             AttnStride dos, AttnStride dqs, AttnStride dks,
                             AttnStride dvs, int batch, int n_heads,
-                            int n_kv_heads, int S, float scale, void* ws) {
+                            int n_kv_heads, int S, int S_kv, float scale,
+                            void* ws) {
   const int sched = attn_sched_mode();
-  const int nrb = S / 256;
   {
-    dim3 grid(nrb * n_heads * batch), block(512);
+    dim3 grid((S / 256) * n_heads * batch), block(512);
     hipLaunchKernelGGL(attn_bwd_dq_kernel<CAUSAL>, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
@@ -1810,12 +1848,14 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                        vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
                        dqs.sb, dqs.sh, dqs.ss,
-                       n_heads, n_heads / n_kv_heads, S, scale, batch, sched);
+                       n_heads, n_heads / n_kv_heads, S, scale, batch, sched,
+                       S_kv);
   }
+  const int nrb = S_kv / 256;
   const bool split = ws != nullptr;
   float* ws_k = (float*)ws;
-  float* ws_v = split ? ws_k + (long)batch * n_heads * S * ATTN_D : nullptr;
-  const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, CAUSAL,
+  float* ws_v = split ? ws_k + (long)batch * n_heads * S_kv * ATTN_D : nullptr;
+  const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S_kv, CAUSAL,
                                      split);
   dim3 grid(nrb * (split ? n_heads : n_kv_heads) * batch), block(512);
   auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
@@ -1825,7 +1865,8 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                      (const float*)lse, (u16*)dv,
                      qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                      dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
-                     n_heads, n_kv_heads, S, scale, ws_v, batch, sched, fold);
+                     n_heads, n_kv_heads, S, scale, ws_v, batch, sched, fold,
+                     S_kv);
   auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
                          : attn_bwd_dk_kernel<CAUSAL, false>;
   hipLaunchKernelGGL(dk_kernel, grid, block, 0, st,
@@ -1835,14 +1876,15 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                      qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
                      vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
                      dks.sb, dks.sh, dks.ss,
-                     n_heads, n_kv_heads, S, scale, ws_k, batch, sched, fold);
+                     n_heads, n_kv_heads, S, scale, ws_k, batch, sched, fold,
+                     S_kv);
   if (split) {
-    const long n_rows = (long)batch * n_kv_heads * S;
+    const long n_rows = (long)batch * n_kv_heads * S_kv;
     hipLaunchKernelGGL(attn_bwd_reduce_kernel,
                        dim3((unsigned)((n_rows + 15) / 16), 2), dim3(256), 0,
                        st, (const float*)ws_k, (const float*)ws_v,
                        (u16*)dk, (u16*)dv, dks.sb, dks.sh, dks.ss,
-                       dvs.sb, dvs.sh, dvs.ss, n_heads, n_kv_heads, S,
+                       dvs.sb, dvs.sh, dvs.ss, n_heads, n_kv_heads, S_kv,
                        n_rows);
   }
 }
@@ -1856,29 +1898,44 @@ struct AttnBwdArgs {
   float scale;
   bool causal;
   bool with_delta;     // compute delta from out/dout first (dense entries)
+  int S_kv = 0;        // k/v rows of a rectangular block; 0 = square (S)
 };
+
+// Shape check of one backward call and the workspace bytes it needs now:
+// -1 for a shape the kernels do not cover (rectangular needs non-causal).
+static long attn_bwd_need(const AttnBwdArgs& a) {
+  if (a.S_kv == 0 || a.S_kv == a.S) {
+    if (!attn_block_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S)) return -1;
+    return attn_bwd_ws_bytes(a.batch, a.n_heads, a.n_kv_heads, a.S, a.causal);
+  }
+  if (!attn_rect_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S, a.S_kv,
+                          a.causal))
+    return -1;
+  return attn_bwd_ws_bytes_rect(a.batch, a.n_heads, a.n_kv_heads, a.S, a.S_kv,
+                                a.causal);
+}
 
 // Launch with the caller's workspace. Nothing is launched unless the
 // workspace covers the path chosen for this call.
 static int launch_bwd_ws(hipStream_t st, const AttnBwdArgs& a, void* ws,
                          long ws_bytes) {
-  if (!attn_block_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S)) return -1;
-  const long need = attn_bwd_ws_bytes(a.batch, a.n_heads, a.n_kv_heads, a.S,
-                                      a.causal);
+  const long need = attn_bwd_need(a);
+  if (need < 0) return -1;
   if (need > 0 && (ws == nullptr || ws_bytes < need)) return -2;
   if (need == 0) ws = nullptr;
+  const int S_kv = a.S_kv ? a.S_kv : a.S;
   if (a.with_delta)
     launch_delta(st, a.out, a.dout, a.delta, a.os, a.dos, a.batch, a.n_heads,
                  a.S);
   if (a.causal)
     launch_bwd_core<true>(st, a.q, a.k, a.v, a.dout, a.lse, a.delta, a.dq,
                           a.dk, a.dv, a.qs, a.ks, a.vs, a.dos, a.dqs, a.dks,
-                          a.dvs, a.batch, a.n_heads, a.n_kv_heads, a.S,
+                          a.dvs, a.batch, a.n_heads, a.n_kv_heads, a.S, S_kv,
                           a.scale, ws);
   else
     launch_bwd_core<false>(st, a.q, a.k, a.v, a.dout, a.lse, a.delta, a.dq,
                            a.dk, a.dv, a.qs, a.ks, a.vs, a.dos, a.dqs, a.dks,
-                           a.dvs, a.batch, a.n_heads, a.n_kv_heads, a.S,
+                           a.dvs, a.batch, a.n_heads, a.n_kv_heads, a.S, S_kv,
                            a.scale, ws);
   return 0;
 }
@@ -1889,9 +1946,8 @@ static int launch_bwd_ws(hipStream_t st, const AttnBwdArgs& a, void* ws,
 // recorded into a graph, so they refuse a capturing stream: callers that
 // capture use the _ws entries with memory from their own allocator.
 static int launch_bwd_transient(hipStream_t st, const AttnBwdArgs& a) {
-  if (!attn_block_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S)) return -1;
-  const long need = attn_bwd_ws_bytes(a.batch, a.n_heads, a.n_kv_heads, a.S,
-                                      a.causal);
+  const long need = attn_bwd_need(a);
+  if (need < 0) return -1;
   if (need == 0) return launch_bwd_ws(st, a, nullptr, 0);
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess ||
@@ -2022,9 +2078,11 @@ extern "C" int attn_bwd_strided_ws(void* stream, const void* q, const void* k,
 //
 // CAUSAL (also on the dq/dv/dk kernels): true is the causal kernel, tiles
 // up to the diagonal, mask on the diagonal band. false compiles the bound,
-// the tile skip and the mask out: every q block visits all S/64 kv tiles
-// (S_q == S_kv == S), for the blocks of ring attention that lie wholly
-// below the diagonal. Pipeline, ring depth, waits and barriers are shared.
+// the tile skip and the mask out: every q block visits all S_kv/64 kv tiles,
+// for the blocks of ring attention that lie wholly below the diagonal. Those
+// may be rectangular: the non-causal kernels take the q length S and the k/v
+// length S_kv apart, the causal ones never read S_kv (S_q == S_kv == S).
+// Pipeline, ring depth, waits and barriers are shared.
 // ===========================================================================
 
 template <bool CAUSAL>
@@ -2036,7 +2094,10 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long k_sb, long k_sh, long k_ss,
     long v_sb, long v_sh, long v_ss,
     long o_sb, long o_sh, long o_ss,
-    int n_heads, int gqa_group, int S, float scale2, int batch, int sched) {
+    int n_heads, int gqa_group, int S, float scale2, int batch, int sched,
+    int S_kv) {
+  // S is the q length: row blocks, qb, the lse row base. S_kv, the k/v
+  // length of a rectangular block, is read by the non-causal kernel alone.
   constexpr int NT = 512;
   const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
                                          sched);
@@ -2080,7 +2141,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   const u16* kbase = k + (long)b * k_sb + (long)hkv * k_sh;
   const u16* vbase = v + (long)b * v_sb + (long)hkv * v_sh;
   // causal: tiles up to the diagonal; non-causal: every kv tile
-  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S / V6_BN;
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
 
   // glds source pointers (swizzle-inverted, advanced per issue)
   const u16* kgp[2];
@@ -2392,6 +2453,59 @@ extern "C" int attn_block_bwd_ws(void* stream, const void* q, const void* k,
   if (!attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
                            batch, n_heads, n_kv_heads, S, scale, causal))
     return -1;
+  return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
+                       ws_bytes);
+}
+
+// Rectangular blocks: S_q query rows against S_kv key rows (each a multiple
+// of 256), non-causal unless S_q == S_kv. The zig-zag ring visits the low
+// half of a K/V shard with all q rows and a whole K/V shard with the high
+// half of the q rows. lse and delta are dense fp32 [B,H,S_q]; dk and dv have
+// S_kv rows. A square shape computes what the square entries compute.
+extern "C" int attn_block_fwd_rect(void* stream, const void* q, const void* k,
+                                   const void* v, void* out, void* lse,
+                                   const long* st, int batch, int n_heads,
+                                   int n_kv_heads, int S_q, int S_kv,
+                                   float scale, int causal) {
+  if (!attn_rect_shape_ok(batch, n_heads, n_kv_heads, S_q, S_kv, causal != 0))
+    return -1;
+  if (!st || !attn_strides_ok(st, 12)) return -1;
+  return launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
+                       st[3], st[4], st[5], st[6], st[7], st[8], st[9],
+                       st[10], st[11], batch, n_heads, n_kv_heads, S_q, scale,
+                       causal != 0, S_kv);
+}
+
+extern "C" int attn_block_bwd_rect(void* stream, const void* q, const void* k,
+                                   const void* v, const void* dout,
+                                   const void* lse, const void* delta,
+                                   void* dq, void* dk, void* dv,
+                                   const long* st, int batch, int n_heads,
+                                   int n_kv_heads, int S_q, int S_kv,
+                                   float scale, int causal) {
+  AttnBwdArgs a;
+  if (S_kv <= 0 ||
+      !attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                           batch, n_heads, n_kv_heads, S_q, scale, causal))
+    return -1;
+  a.S_kv = S_kv;
+  return launch_bwd_transient(reinterpret_cast<hipStream_t>(stream), a);
+}
+
+extern "C" int attn_block_bwd_rect_ws(void* stream, const void* q,
+                                      const void* k, const void* v,
+                                      const void* dout, const void* lse,
+                                      const void* delta, void* dq, void* dk,
+                                      void* dv, const long* st, int batch,
+                                      int n_heads, int n_kv_heads, int S_q,
+                                      int S_kv, float scale, int causal,
+                                      void* ws, long ws_bytes) {
+  AttnBwdArgs a;
+  if (S_kv <= 0 ||
+      !attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                           batch, n_heads, n_kv_heads, S_q, scale, causal))
+    return -1;
+  a.S_kv = S_kv;
   return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
                        ws_bytes);
 }

@@ -437,6 +437,39 @@ __global__ void rope_packed_kernel(const uint4* x, uint4* out,
   }
 }
 
+// rope_packed_kernel at shard positions: local row s = t % S sits at
+// pos_a + s while s < seg_len and at pos_b + (s - seg_len) after it. One
+// segment (S == seg_len) is a contiguous sequence shard at offset pos_a, two
+// (S == 2*seg_len) the zig-zag shard of context parallelism. Same pair
+// ownership as rope_packed_kernel, so x and out may alias.
+__global__ void rope_packed_at_kernel(const uint4* x, uint4* out,
+                                      const float* __restrict__ inv_freq,
+                                      long total_vec, int vec_per_half,
+                                      int n_rot, long x_row_vec,
+                                      long out_row_vec, int S, int D,
+                                      float sign, int seg_len, int pos_a,
+                                      int pos_b) {
+  const int HALF = D / 2;
+  for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < total_vec;
+       g += gridDim.x * (long)blockDim.x) {
+    const long per_head = vec_per_half;
+    const long head_g = g / per_head;
+    const int i0 = (int)(g % per_head) * 8;
+    const long t = head_g / n_rot;
+    const int h = (int)(head_g % n_rot);
+    const int s = (int)(t % S);
+    const int pos = s < seg_len ? pos_a + s : pos_b + (s - seg_len);
+    const long xb = t * x_row_vec + (long)h * (D / 8);
+    const long ob_ = t * out_row_vec + (long)h * (D / 8);
+    BF8 a; a.v = x[xb + i0 / 8];
+    BF8 b; b.v = x[xb + (HALF + i0) / 8];
+    BF8 oa, ob;
+    rope_rotate8(a, b, oa, ob, inv_freq, i0, pos, sign);
+    out[ob_ + i0 / 8] = oa.v;
+    out[ob_ + (HALF + i0) / 8] = ob.v;
+  }
+}
+
 // ===========================================================================
 // SwiGLU: out = silu(g) * u, elementwise over [*, F].
 // bwd recomputes silu from g (g, u are GEMM outputs already saved).
@@ -1537,6 +1570,33 @@ int rope_packed(void* stream, const void* x, void* out, const void* inv_freq,
                      (const uint4*)x, (uint4*)out, (const float*)inv_freq,
                      total_vec, vec_per_half, n_rot, x_row / 8, out_row / 8,
                      S, D, sign);
+  return 0;
+}
+
+// rope_packed at shard positions (rope_packed_at_kernel): S == seg_len is one
+// segment at pos_a (pos_b unused), S == 2*seg_len two segments. Positions
+// become floats in the kernel, so every one must stay at or below 2^24.
+int rope_packed_at(void* stream, const void* x, void* out,
+                   const void* inv_freq, long n_tokens, int n_rot, long x_row,
+                   long out_row, int S, int D, float sign, int seg_len,
+                   int pos_a, int pos_b) {
+  if (D <= 0 || D % 16 != 0 || n_rot <= 0 || S <= 0) return -1;
+  if (x_row % 8 != 0 || out_row % 8 != 0 || x_row < (long)n_rot * D ||
+      out_row < (long)n_rot * D)
+    return -1;
+  if (seg_len <= 0 || (S != seg_len && S != 2L * seg_len)) return -1;
+  const long pos_max = 1L << 24;
+  if (pos_a < 0 || (long)pos_a + seg_len > pos_max) return -1;
+  if (S != seg_len && (pos_b < 0 || (long)pos_b + seg_len > pos_max))
+    return -1;
+  if (n_tokens <= 0) return 0;
+  const int vec_per_half = (D / 2) / 8;
+  const long total_vec = n_tokens * (long)n_rot * vec_per_half;
+  dim3 grid(elementwise_grid(total_vec)), block(BLOCK);
+  hipLaunchKernelGGL(rope_packed_at_kernel, grid, block, 0, STREAM,
+                     (const uint4*)x, (uint4*)out, (const float*)inv_freq,
+                     total_vec, vec_per_half, n_rot, x_row / 8, out_row / 8,
+                     S, D, sign, seg_len, pos_a, pos_b);
   return 0;
 }
 

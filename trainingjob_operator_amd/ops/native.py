@@ -67,6 +67,9 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.rope_at, [vp, vp, vp, vp, l, i, i, i, f, i], i)
     _sig(lib.rope_at_dev, [vp, vp, vp, vp, l, i, i, i, f, vp], i)
     _sig(lib.rope_packed, [vp, vp, vp, vp, l, i, l, l, i, i, f], i)
+    # rope_packed + (seg_len, pos_a, pos_b): rows at shard positions
+    _sig(lib.rope_packed_at, [vp, vp, vp, vp, l, i, l, l, i, i, f, i, i, i],
+         i)
     _sig(lib.gemv_bf16, [vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_swiglu, [vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_moe_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i], i)
@@ -125,6 +128,15 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
                                    vp, lp, i, i, i, i, f, vp, l], i)
     _sig(lib.attn_block_bwd_ws, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, lp,
                                  i, i, i, i, f, i, vp, l], i)
+    # rectangular non-causal blocks: (S_q, S_kv) in place of S; lse and delta
+    # are [B,H,S_q], dk/dv and the workspace rows follow S_kv
+    _sig(lib.attn_block_fwd_rect, [vp, vp, vp, vp, vp, vp, lp,
+                                   i, i, i, i, i, f, i], i)
+    _sig(lib.attn_block_bwd_rect, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, lp,
+                                   i, i, i, i, i, f, i], i)
+    _sig(lib.attn_block_bwd_rect_ws, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      lp, i, i, i, i, i, f, i, vp, l], i)
+    _sig(lib.attn_bwd_ws_bytes_rect, [i, i, i, i, i, i], l)
     # block-id decode of the scheduled attention kernels (host callable):
     # (sched 0 legacy | 1 balanced, id, row blocks, heads, batch) ->
     # rank, head, batch

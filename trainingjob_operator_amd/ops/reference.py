@@ -55,6 +55,22 @@ def rope_rotate(x: torch.Tensor, inv_freq: torch.Tensor, seq_len: int,
     return torch.cat([o1, o2], dim=-1).to(x.dtype)
 
 
+def rope_at(x: torch.Tensor, inv_freq: torch.Tensor, positions: torch.Tensor,
+            sign: float = 1.0) -> torch.Tensor:
+    """Twin of rope_packed_at: x [..., S, n_heads, D], positions [S] (the
+    global token index of every local row, e.g. cp_shard_positions); neox
+    half-rotation in fp32, result in x.dtype. Differentiable."""
+    half = x.shape[-1] // 2
+    assert positions.shape == (x.shape[-3],), (positions.shape, x.shape)
+    ang = positions.to(x.device).float()[:, None] * inv_freq[None, :].float()
+    cos = torch.cos(ang)[:, None, :]                # [S, 1, half]
+    sin = torch.sin(ang)[:, None, :] * sign
+    xf = x.float()
+    x1, x2 = xf[..., :half], xf[..., half:]
+    return torch.cat([x1 * cos - x2 * sin,
+                      x1 * sin + x2 * cos], dim=-1).to(x.dtype)
+
+
 def swiglu_fwd(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     gf = g.float()
     return (gf * torch.sigmoid(gf) * u.float()).to(g.dtype)
