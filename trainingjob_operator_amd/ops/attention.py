@@ -68,6 +68,21 @@ either way. AITJ_ATTN_BWD_FOLD=0 never folds, 1 always folds causal
 launches, unset follows the measured rule (fold when the dv/dk grid has at
 most one workgroup per CU - the flagship step does); read on every call.
 `lib.attn_bwd_strips_decode` is the host copy of the ownership function.
+
+Paired dK/dV strips (`attn_bwd_pair`, AITJ_ATTN_BWD_FOLD=2): the causal
+unsplit `attn_bwd_dv_pair_kernel` / `attn_bwd_dk_pair_kernel` run the two
+half-blocks of the fold one after the other, and the two waves of a SIMD
+(w and w+4) share one strip: each computes one 32-row half of every q
+tile, they swap the packed P / dS fragments through 16 KB of LDS, and each
+accumulates two of the strip's four 32-column d subtiles over all four q
+chunks. Every accumulator keeps its order, so dk and dv are bit-identical
+again, and every workgroup walks S/64 + 2 tile steps per q head with both
+waves of each SIMD busy. Split and non-causal launches never pair (2 then
+means unset). Unset follows the measured rule per kernel: where the grid
+has at most one workgroup per CU dk pairs and dv folds (the flagship step
+does), above that both keep the identity. `lib.attn_bwd_pair_decode` is
+the host copy of the ownership function and `lib.attn_bwd_fold_mode` says
+which ownership a launch of a given shape gets.
 """
 from __future__ import annotations
 

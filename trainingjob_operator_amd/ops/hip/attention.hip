@@ -179,6 +179,55 @@ __host__ __device__ __forceinline__ AttnStrips attn_bwd_strips(
   return s;
 }
 
+// ---------------------------------------------------------------------------
+// PAIR: the third ownership (causal, unsplit dv/dk only; its own kernels).
+//
+// The fold balances the workgroups by leaving a SIMD one active wave for
+// almost every tile step, and a lone wave keeps the MFMA pipe about 20 %
+// busy. But a strip's chain is four chains: the accumulators of the four
+// 32-column d subtiles ds are independent, each ordered only by (q head,
+// q tile, q chunk c), and the S^T / dP products of a tile's two 32-row subs
+// are independent too. So the two waves of a SIMD, w and w + 4, share one
+// strip: wave role r = wid >> 2 computes sub r of every tile, which makes
+// the packed P / dS fragments of chunks 2r and 2r + 1, the partners swap
+// them through LDS, and each accumulates ds 2r and 2r + 1 over chunks
+// 0 .. 3 ascending. Every accumulator meets the same fragments in the same
+// order as with one owner, so dk and dv keep their bits.
+//
+// Workgroup rank runs two phases one after the other: half-block rank
+// (heavy), then half-block 2n-1-rank (light), four strips each, walked
+// from the half-block's own first tile 2*hb: (4n - 2*rank) + (2*rank + 2)
+// = 4n + 2 tile steps per q head whatever the rank, both waves of every
+// SIMD busy in all of them (but for the half-block's first tile, which
+// strips 2 and 3 sit out).
+// ---------------------------------------------------------------------------
+
+#define ATTN_STRIPS_PAIR 2
+
+// sub: the 32-row half of each q tile this wave computes; ds0: the first of
+// the two d subtiles it accumulates; peer: the wave whose fragments it reads.
+struct AttnPair { int kv0w, qt0, sub, ds0, peer; };
+
+__host__ __device__ __forceinline__ AttnPair attn_bwd_pair(
+    int rank, int phase, int wid, int n_row_blocks) {
+  AttnPair p;
+  const int hb = phase == 0 ? rank : 2 * n_row_blocks - 1 - rank;
+  p.kv0w = hb * 128 + (wid & 3) * 32;
+  p.qt0 = hb * 2;
+  p.sub = wid >> 2;
+  p.ds0 = (wid >> 2) * 2;
+  p.peer = wid ^ 4;
+  return p;
+}
+
+// Exchange area of the pair kernels: one 16-byte fragment per lane, chunk c
+// of the strip that waves w and w + 4 share. Wave wid writes chunks
+// 2*sub and 2*sub + 1 and reads all four back, its partner's among them.
+#define ATTN_PAIR_XCH_U4 (4 * 4 * 64)        // 16 KB
+__host__ __device__ __forceinline__ int attn_pair_xch(int wid, int c) {
+  return ((wid & 3) * 4 + c) * 64;
+}
+
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ out,
@@ -1637,7 +1686,405 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// dV and dK with PAIR ownership (attn_bwd_pair): causal, unsplit. Same grid,
+// staging and element arithmetic as attn_bwd_dv_kernel<true, false> and
+// attn_bwd_dk_kernel<true, false>; what differs is who computes what.
+//
+// Barriers: every wave reaches, per phase and q head, one barrier after the
+// first staging and two per tile (after the fragment exchange writes, and
+// the end-of-tile one), all outside `if (active)`; qt0, qtn and the head
+// range are workgroup-uniform, so the count is equal for the eight waves
+// on every path, the last tile (no have_next) and the phase change
+// included. Partners share kv0w, hence `active`, so the exchange is skipped
+// by both or by neither. A wave rewrites its exchange chunks only after the
+// end-of-tile barrier that follows its partner's read of them.
+//
+// The A operand of d subtile ds0 + j sits ds0 * 32 rows further into the
+// transposed image: vt_byte(ds0 * 32 + d, kv) == ds0 * 32 * VT_PITCH_B +
+// vt_byte(d, kv) for ds0 in {0, 2}, because 64 * VT_PITCH_B = 9 * 1024
+// leaves the XORed slot bits alone and the key of m + 8 is the key of m.
+// ---------------------------------------------------------------------------
 
+__global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
+    const u16* __restrict__ q, const u16* __restrict__ k,
+    const u16* __restrict__ dout, const float* __restrict__ lse,
+    u16* __restrict__ dv,
+    long q_sb, long q_sh, long q_ss,
+    long k_sb, long k_sh, long k_ss,
+    long do_sb, long do_sh, long do_ss,
+    long dv_sb, long dv_sh, long dv_ss,
+    int n_heads, int n_kv_heads, int S, float scale, int batch, int sched) {
+  const int nrb = S / 256;
+  const AttnBlock blk = attn_sched_block(blockIdx.x, nrb, n_kv_heads, batch,
+                                         sched);
+  const int gqa_group = n_heads / n_kv_heads;
+  const int hkv = blk.head;
+  const int b = blk.batch;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int low = lane & 31;
+  const int hi = lane >> 5;
+  const float scale2 = scale * 1.4426950408889634f;
+
+  __shared__ __attribute__((aligned(16))) u16 lds[2][BV_BUF_U16];
+  __shared__ __attribute__((aligned(16))) uint4 xch[ATTN_PAIR_XCH_U4];
+  char* lds0 = reinterpret_cast<char*>(&lds[0][0]);
+  char* lds1 = reinterpret_cast<char*>(&lds[1][0]);
+  const int DOTOFF = BV_Q_U16 * 2;
+  const int LSEOFF = (BV_Q_U16 + BV_DOT_U16) * 2;
+
+  const int qtn = S / 64;
+  const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
+  uint4 dtst[2];
+
+#pragma unroll 1
+  for (int phase = 0; phase < 2; ++phase) {
+    const AttnPair pr = attn_bwd_pair(blk.rank, phase, wu64, nrb);
+    const int kv0w = pr.kv0w;
+    const int kvrow = kv0w + low;            // this lane's kv row
+    const int sub = pr.sub;
+    const int aoff = pr.ds0 * 32 * VT_PITCH_B;
+
+    const u16* kptr =
+        k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
+    F8 kf[8];
+#pragma unroll
+    for (int kc = 0; kc < 8; ++kc)
+      kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
+
+    f32x16 dvacc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dvacc[j][r] = 0.f;
+
+    const int qt0 = pr.qt0;
+
+    for (int g = 0; g < gqa_group; ++g) {
+      const int h = hkv * gqa_group + g;
+      const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
+      const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
+      const float* lbase = lse + ((long)b * n_heads + h) * S;
+
+      const u16* qgp[2];
+      const u16* dtp[2];
+      {
+        const int idx0 = tid, idx1 = 512 + tid;
+        const int L0 = idx0 * 16, L1 = idx1 * 16;
+        const int r0 = L0 >> 8, r1 = L1 >> 8;
+        const int in0 = (((L0 & 255) ^ ((r0 & 15) << 4)) >> 1);
+        const int in1 = (((L1 & 255) ^ ((r1 & 15) << 4)) >> 1);
+        qgp[0] = qbase + (long)(qt0 * 64 + r0) * q_ss + in0;
+        qgp[1] = qbase + (long)(qt0 * 64 + r1) * q_ss + in1;
+        const int rp2 = (tid >> 4) * 2;
+        const int c8 = (tid & 15) * 8;
+        dtp[0] = dobase + (long)(qt0 * 64 + rp2) * do_ss + c8;
+        dtp[1] = dobase + (long)(qt0 * 64 + rp2 + 1) * do_ss + c8;
+      }
+      const long qstep = (long)64 * q_ss;
+      const long dostep = (long)64 * do_ss;
+
+      BV_STAGE_IN(0, qt0)
+      BV_WRITE_DOT(lds0)
+      __syncthreads();
+
+      int cur = 0;
+      for (int qt = qt0; qt < qtn; ++qt) {
+        const bool have_next = (qt + 1) < qtn;
+        if (have_next) BV_STAGE_IN(cur ^ 1, qt + 1)
+
+        char* qb_ = cur ? lds1 : lds0;
+        char* dob = qb_ + DOTOFF;
+        const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
+        const bool active = qt * 64 + 63 >= kv0w;
+        const bool need_mask = qt * 64 < kv0w + 32;
+
+        union PF { bf16x8 v; unsigned u[4]; uint4 q4; } pf[4];
+        if (active) {
+          f32x16 s;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+          for (int kc = 0; kc < 8; ++kc) {
+            bf16x8 a = *reinterpret_cast<const bf16x8*>(
+                &qb_[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kc].v, s,
+                                                        0, 0, 0);
+          }
+          // P = 2^(s*scale2 - lse2[q]); mask q < kv
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;   // q within sub
+            float x = s[r] * scale2 - lse2t[sub * 32 + qr];
+            if (need_mask && qt * 64 + sub * 32 + qr < kvrow) x = -1e30f;
+            s[r] = exp2_raw(x);
+          }
+          // repack P (C[q][kv]) -> B-fragments [k=q chunk][n=kv], chunks
+          // 2*sub and 2*sub + 1, into the exchange area
+#pragma unroll
+          for (int cc = 0; cc < 2; ++cc) {
+            const int pb = cc * 8;
+            unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
+            unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
+            unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
+            unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
+            auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+            auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+            PF f;
+            f.u[0] = r02[0];
+            f.u[1] = r13[0];
+            f.u[2] = r02[1];
+            f.u[3] = r13[1];
+            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.q4;
+          }
+        }
+        v7_barrier();                        // fragments of both subs written
+        if (active) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            pf[c].q4 = xch[attn_pair_xch(wu64, c) + lane];
+        }
+        if (have_next) {
+          char* nb = cur ? lds0 : lds1;
+          BV_WRITE_DOT(nb)
+        }
+        if (active) {
+          // dV^T += dO^T @ P over 4 q chunks x this wave's 2 d subtiles
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              bf16x8 af = *reinterpret_cast<const bf16x8*>(
+                  &dob[aoff + vt_byte(j * 32 + low, c * 16 + hi * 8)]);
+              dvacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  af, pf[c].v, dvacc[j], 0, 0, 0);
+            }
+          }
+        }
+        __syncthreads();
+        cur ^= 1;
+      }
+    }
+
+    // this wave's two d subtiles of the strip's rows
+    u16* dvrow =
+        dv + (long)b * dv_sb + (long)hkv * dv_sh + (long)kvrow * dv_ss;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d0 = 8 * g + 4 * hi + 32 * (pr.ds0 + j);
+        const unsigned w0 = cvt_pk_bf16(dvacc[j][4 * g + 0],
+                                        dvacc[j][4 * g + 1]);
+        const unsigned w1 = cvt_pk_bf16(dvacc[j][4 * g + 2],
+                                        dvacc[j][4 * g + 3]);
+        uint2 wv;
+        wv.x = w0;
+        wv.y = w1;
+        *reinterpret_cast<uint2*>(dvrow + d0) = wv;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
+    const u16* __restrict__ q, const u16* __restrict__ k,
+    const u16* __restrict__ v, const u16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    u16* __restrict__ dk,
+    long q_sb, long q_sh, long q_ss,
+    long k_sb, long k_sh, long k_ss,
+    long v_sb, long v_sh, long v_ss,
+    long do_sb, long do_sh, long do_ss,
+    long dk_sb, long dk_sh, long dk_ss,
+    int n_heads, int n_kv_heads, int S, float scale, int batch, int sched) {
+  const int nrb = S / 256;
+  const AttnBlock blk = attn_sched_block(blockIdx.x, nrb, n_kv_heads, batch,
+                                         sched);
+  const int gqa_group = n_heads / n_kv_heads;
+  const int hkv = blk.head;
+  const int b = blk.batch;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int low = lane & 31;
+  const int hi = lane >> 5;
+  const float scale2 = scale * 1.4426950408889634f;
+
+  __shared__ __attribute__((aligned(16))) u16 lds[2][BK_BUF_U16];
+  __shared__ __attribute__((aligned(16))) uint4 xch[ATTN_PAIR_XCH_U4];
+  char* lds0 = reinterpret_cast<char*>(&lds[0][0]);
+  char* lds1 = reinterpret_cast<char*>(&lds[1][0]);
+  const int DOOFF = BK_Q_U16 * 2;
+  const int QTOFF = (BK_Q_U16 + BK_DO_U16) * 2;
+  const int LSEOFF = (BK_Q_U16 + BK_DO_U16 + BK_QT_U16) * 2;
+  const int DLTOFF = LSEOFF + BK_LSE_U16 * 2;
+
+  const int qtn = S / 64;
+  const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
+  uint4 qtst[2];
+
+#pragma unroll 1
+  for (int phase = 0; phase < 2; ++phase) {
+    const AttnPair pr = attn_bwd_pair(blk.rank, phase, wu64, nrb);
+    const int kv0w = pr.kv0w;
+    const int kvrow = kv0w + low;
+    const int sub = pr.sub;
+    const int aoff = pr.ds0 * 32 * VT_PITCH_B;
+
+    const u16* kptr =
+        k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
+    const u16* vptr =
+        v + (long)b * v_sb + (long)hkv * v_sh + (long)kvrow * v_ss;
+    F8 kf[8], vf[8];
+#pragma unroll
+    for (int kc = 0; kc < 8; ++kc) {
+      kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
+      vf[kc].u = *reinterpret_cast<const uint4*>(vptr + kc * 16 + hi * 8);
+    }
+
+    f32x16 dkacc[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dkacc[j][r] = 0.f;
+
+    const int qt0 = pr.qt0;
+
+    for (int g = 0; g < gqa_group; ++g) {
+      const int h = hkv * gqa_group + g;
+      const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
+      const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
+      const float* lbase = lse + ((long)b * n_heads + h) * S;
+      const float* dbase = delta + ((long)b * n_heads + h) * S;
+
+      const u16* qgp[2];
+      const u16* dgp[2];
+      const u16* qtp[2];
+      {
+        const int idx0 = tid, idx1 = 512 + tid;
+        const int L0 = idx0 * 16, L1 = idx1 * 16;
+        const int r0 = L0 >> 8, r1 = L1 >> 8;
+        const int in0 = (((L0 & 255) ^ ((r0 & 15) << 4)) >> 1);
+        const int in1 = (((L1 & 255) ^ ((r1 & 15) << 4)) >> 1);
+        qgp[0] = qbase + (long)(qt0 * 64 + r0) * q_ss + in0;
+        qgp[1] = qbase + (long)(qt0 * 64 + r1) * q_ss + in1;
+        dgp[0] = dobase + (long)(qt0 * 64 + r0) * do_ss + in0;
+        dgp[1] = dobase + (long)(qt0 * 64 + r1) * do_ss + in1;
+        const int rp2 = (tid >> 4) * 2;
+        const int c8 = (tid & 15) * 8;
+        qtp[0] = qbase + (long)(qt0 * 64 + rp2) * q_ss + c8;
+        qtp[1] = qbase + (long)(qt0 * 64 + rp2 + 1) * q_ss + c8;
+      }
+      const long qstep = (long)64 * q_ss;
+      const long dostep = (long)64 * do_ss;
+
+      BK_STAGE_IN(0, qt0)
+      BK_WRITE_QT(lds0)
+      __syncthreads();
+
+      int cur = 0;
+      for (int qt = qt0; qt < qtn; ++qt) {
+        const bool have_next = (qt + 1) < qtn;
+        if (have_next) BK_STAGE_IN(cur ^ 1, qt + 1)
+
+        char* qb_ = cur ? lds1 : lds0;
+        char* dob = qb_ + DOOFF;
+        char* qtb = qb_ + QTOFF;
+        const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
+        const float* dltt = reinterpret_cast<const float*>(qb_ + DLTOFF);
+        const bool active = qt * 64 + 63 >= kv0w;
+        const bool need_mask = qt * 64 < kv0w + 32;
+
+        union PF { bf16x8 v; unsigned u[4]; uint4 q4; } pf[4];
+        if (active) {
+          f32x16 s, dp;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+          for (int kc = 0; kc < 8; ++kc) {
+            bf16x8 a = *reinterpret_cast<const bf16x8*>(
+                &qb_[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kc].v, s,
+                                                        0, 0, 0);
+            bf16x8 a2 = *reinterpret_cast<const bf16x8*>(
+                &dob[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, vf[kc].v, dp,
+                                                         0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            float x = s[r] * scale2 - lse2t[sub * 32 + qr];
+            if (need_mask && qt * 64 + sub * 32 + qr < kvrow) x = -1e30f;
+            const float p = exp2_raw(x);
+            s[r] = p * (dp[r] - dltt[sub * 32 + qr]) * scale;
+          }
+#pragma unroll
+          for (int cc = 0; cc < 2; ++cc) {
+            const int pb = cc * 8;
+            unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
+            unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
+            unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
+            unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
+            auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+            auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+            PF f;
+            f.u[0] = r02[0];
+            f.u[1] = r13[0];
+            f.u[2] = r02[1];
+            f.u[3] = r13[1];
+            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.q4;
+          }
+        }
+        v7_barrier();                        // fragments of both subs written
+        if (active) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            pf[c].q4 = xch[attn_pair_xch(wu64, c) + lane];
+        }
+        if (have_next) {
+          char* nb = cur ? lds0 : lds1;
+          BK_WRITE_QT(nb)
+        }
+        if (active) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              bf16x8 af = *reinterpret_cast<const bf16x8*>(
+                  &qtb[aoff + vt_byte(j * 32 + low, c * 16 + hi * 8)]);
+              dkacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  af, pf[c].v, dkacc[j], 0, 0, 0);
+            }
+          }
+        }
+        __syncthreads();
+        cur ^= 1;
+      }
+    }
+
+    u16* dkrow =
+        dk + (long)b * dk_sb + (long)hkv * dk_sh + (long)kvrow * dk_ss;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d0 = 8 * g + 4 * hi + 32 * (pr.ds0 + j);
+        const unsigned w0 = cvt_pk_bf16(dkacc[j][4 * g + 0],
+                                        dkacc[j][4 * g + 1]);
+        const unsigned w1 = cvt_pk_bf16(dkacc[j][4 * g + 2],
+                                        dkacc[j][4 * g + 3]);
+        uint2 wv;
+        wv.x = w0;
+        wv.y = w1;
+        *reinterpret_cast<uint2*>(dkrow + d0) = wv;
+      }
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------
 // launchers
@@ -1751,11 +2198,14 @@ static bool attn_bwd_use_split(int batch, int n_heads, int n_kv_heads, int S,
   return wgs < (long)(causal ? 2 : 1) * ATTN_NUM_CUS;
 }
 
-// Whether the causal dv/dk workgroups own folded strips (attn_bwd_strips).
-// The one place that decides; read on every call. AITJ_ATTN_BWD_FOLD: 0 =
-// never, 1 = always (causal); unset or anything else = the measured rule
-// below. The fold changes no bit of dk or dv, so unlike the split the
-// default may use it. Non-causal launches never fold: equal work already.
+// Which ownership the causal dv/dk workgroups take: identity, folded strips
+// (attn_bwd_strips) or pairs (attn_bwd_pair), per kernel. The one place
+// that decides; read on every call. AITJ_ATTN_BWD_FOLD: 0 = identity, 1 =
+// fold (causal), 2 = pair (causal and unsplit; a split launch takes the
+// rule below instead); unset or anything else = the measured rule below.
+// Neither fold nor pair changes a bit of dk or dv, so unlike the split the
+// default may use them. Non-causal launches never fold or pair: equal work
+// already.
 //
 // The fold evens out the work of the waves inside one workgroup; a
 // workgroup still walks 4n - 2*rank tile steps per head, the longest as
@@ -1771,14 +2221,64 @@ static bool attn_bwd_use_split(int batch, int n_heads, int n_kv_heads, int S,
 //            8 wg/CU   (B=4) 1892 -> 2446   16 wg/CU (B=8) 4235 -> 5369
 // So the rule folds when the dv/dk grid has at most one workgroup per CU.
 // Between 1 and 2 per CU nothing was measured.
+//
+// The pair (the partners of a SIMD share one strip, every workgroup walks
+// 4n + 2 steps with both waves busy) is a long workgroup like the fold's
+// and loses to the identity's backfill in the same places. Unsplit, us,
+// identity / fold / pair, two runs averaged
+// (profiles/r08_dkdv_pair.md):
+//   dv  B=1  521 /  417 /  425    B=2  568 /  438 /  445
+//       B=4  691 /  803 /  963    B=8 1384 / 1748 / 2004
+//   dk  B=1  808 /  726 /  588    B=2  862 /  774 /  620
+//       B=4 1039 / 1310 / 1284    B=8 2099 / 2720 / 2661
+// dk pairs where it folded before (at most one workgroup per CU): -19 to -20 %.
+// dv does not: its tile step has too little MFMA work (8 + 8 per wave) to
+// carry the second barrier, and the pair reads 7 us behind the fold there
+// and 11 us behind it in the step trace. So unset gives dk the pair and dv
+// the fold.
+#define ATTN_BWD_DV 0
+#define ATTN_BWD_DK 1
 static int attn_bwd_use_fold(int batch, int n_heads, int n_kv_heads, int S,
-                             bool causal, bool split) {
+                             bool causal, bool split, int kernel) {
   if (!causal) return ATTN_STRIPS_IDENTITY;
   const char* e = std::getenv("AITJ_ATTN_BWD_FOLD");
   if (e && std::strcmp(e, "0") == 0) return ATTN_STRIPS_IDENTITY;
   if (e && std::strcmp(e, "1") == 0) return ATTN_STRIPS_FOLD;
+  if (e && std::strcmp(e, "2") == 0 && !split) return ATTN_STRIPS_PAIR;
   const long wgs = (long)batch * (split ? n_heads : n_kv_heads) * (S / 256);
-  return wgs <= ATTN_NUM_CUS ? ATTN_STRIPS_FOLD : ATTN_STRIPS_IDENTITY;
+  if (wgs > ATTN_NUM_CUS) return ATTN_STRIPS_IDENTITY;
+  if (split || kernel != ATTN_BWD_DK) return ATTN_STRIPS_FOLD;
+  return ATTN_STRIPS_PAIR;
+}
+
+// The ownership a launch of this shape gets right now (0 identity, 1 fold,
+// 2 pair), for kernel 0 = dv, 1 = dk. Host only.
+extern "C" int attn_bwd_fold_mode(int batch, int n_heads, int n_kv_heads,
+                                  int S, int causal, int split, int kernel) {
+  return attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, causal != 0,
+                           split != 0, kernel);
+}
+
+// Host-callable pair ownership (tests/test_attention_pair_cpu.py): workgroup
+// rank, phase 0 (heavy half-block) or 1 (light), wave, row blocks -> the
+// wave's first kv row, the phase's first q tile, the 32-row sub of each tile
+// the wave computes, the half-open range [ds0, ds1) of d subtiles it
+// accumulates, and the wave whose exchange chunks it reads. Returns nonzero
+// for arguments outside the launch.
+extern "C" int attn_bwd_pair_decode(int rank, int phase, int wid,
+                                    int n_row_blocks, int* kv0w, int* qt0,
+                                    int* sub, int* ds0, int* ds1, int* peer) {
+  if (n_row_blocks <= 0 || rank < 0 || rank >= n_row_blocks || wid < 0 ||
+      wid >= 8 || phase < 0 || phase > 1)
+    return -1;
+  const AttnPair p = attn_bwd_pair(rank, phase, wid, n_row_blocks);
+  *kv0w = p.kv0w;
+  *qt0 = p.qt0;
+  *sub = p.sub;
+  *ds0 = p.ds0;
+  *ds1 = p.ds0 + 2;
+  *peer = p.peer;
+  return 0;
 }
 
 // Host-callable strip ownership (tests/test_attention_fold_cpu.py). fold: 0
@@ -1855,29 +2355,51 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
   const bool split = ws != nullptr;
   float* ws_k = (float*)ws;
   float* ws_v = split ? ws_k + (long)batch * n_heads * S_kv * ATTN_D : nullptr;
-  const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S_kv, CAUSAL,
-                                     split);
+  const int fold_v = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S_kv,
+                                       CAUSAL, split, ATTN_BWD_DV);
+  const int fold_k = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S_kv,
+                                       CAUSAL, split, ATTN_BWD_DK);
   dim3 grid(nrb * (split ? n_heads : n_kv_heads) * batch), block(512);
-  auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
-                         : attn_bwd_dv_kernel<CAUSAL, false>;
-  hipLaunchKernelGGL(dv_kernel, grid, block, 0, st,
-                     (const u16*)q, (const u16*)k, (const u16*)dout,
-                     (const float*)lse, (u16*)dv,
-                     qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                     dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
-                     n_heads, n_kv_heads, S, scale, ws_v, batch, sched, fold,
-                     S_kv);
-  auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
-                         : attn_bwd_dk_kernel<CAUSAL, false>;
-  hipLaunchKernelGGL(dk_kernel, grid, block, 0, st,
-                     (const u16*)q, (const u16*)k, (const u16*)v,
-                     (const u16*)dout, (const float*)lse,
-                     (const float*)delta, (u16*)dk,
-                     qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                     vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
-                     dks.sb, dks.sh, dks.ss,
-                     n_heads, n_kv_heads, S, scale, ws_k, batch, sched, fold,
-                     S_kv);
+  if (fold_v == ATTN_STRIPS_PAIR) {          // causal and unsplit only
+    hipLaunchKernelGGL(attn_bwd_dv_pair_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)dout,
+                       (const float*)lse, (u16*)dv,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
+                       n_heads, n_kv_heads, S, scale, batch, sched);
+  } else {
+    auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
+                           : attn_bwd_dv_kernel<CAUSAL, false>;
+    hipLaunchKernelGGL(dv_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)dout,
+                       (const float*)lse, (u16*)dv,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
+                       n_heads, n_kv_heads, S, scale, ws_v, batch, sched,
+                       fold_v, S_kv);
+  }
+  if (fold_k == ATTN_STRIPS_PAIR) {
+    hipLaunchKernelGGL(attn_bwd_dk_pair_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)v,
+                       (const u16*)dout, (const float*)lse,
+                       (const float*)delta, (u16*)dk,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
+                       dks.sb, dks.sh, dks.ss,
+                       n_heads, n_kv_heads, S, scale, batch, sched);
+  } else {
+    auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
+                           : attn_bwd_dk_kernel<CAUSAL, false>;
+    hipLaunchKernelGGL(dk_kernel, grid, block, 0, st,
+                       (const u16*)q, (const u16*)k, (const u16*)v,
+                       (const u16*)dout, (const float*)lse,
+                       (const float*)delta, (u16*)dk,
+                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
+                       dks.sb, dks.sh, dks.ss,
+                       n_heads, n_kv_heads, S, scale, ws_k, batch, sched,
+                       fold_k, S_kv);
+  }
   if (split) {
     const long n_rows = (long)batch * n_kv_heads * S_kv;
     hipLaunchKernelGGL(attn_bwd_reduce_kernel,

@@ -146,6 +146,13 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # identity | 1 fold, workgroup rank, wave, row blocks) -> the wave's
     # first kv row, the workgroup's first q tile
     _sig(lib.attn_bwd_strips_decode, [i, i, i, i, ip, ip], i)
+    # pair ownership of the causal unsplit dv/dk workgroups (host callable):
+    # (workgroup rank, phase 0 heavy | 1 light, wave, row blocks) -> first kv
+    # row, first q tile, sub computed, [ds0, ds1) accumulated, partner wave
+    _sig(lib.attn_bwd_pair_decode, [i, i, i, i, ip, ip, ip, ip, ip, ip], i)
+    # (batch, heads, kv heads, S, causal, split, kernel 0 dv | 1 dk) -> the
+    # ownership a launch gets now: 0 identity, 1 fold, 2 pair
+    _sig(lib.attn_bwd_fold_mode, [i, i, i, i, i, i, i], i)
     _sig(lib.mfma_probe32, [vp, vp, vp, vp])
     assert lib.hipops_arch_check() == 950
     _lib = lib
