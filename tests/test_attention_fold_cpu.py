@@ -113,3 +113,25 @@ def test_out_of_range_arguments_are_refused():
     assert lib.attn_bwd_strips_decode(FOLD, 0, 0, 0, p, p) != 0
     assert lib.attn_bwd_strips_decode(2, 0, 0, 16, p, p) != 0
     assert lib.attn_bwd_strips_decode(-1, 0, 0, 16, p, p) != 0
+
+
+@pytest.mark.parametrize("causal", [0, 1])
+def test_square_workspace_is_the_rectangular_one(monkeypatch, causal):
+    """attn_bwd_ws_bytes(S) is attn_bwd_ws_bytes_rect(S, S): one shape check
+    and one size rule serve the square and the rectangular entries."""
+    monkeypatch.setenv("AITJ_ATTN_BWD_SPLIT", "1")
+    lib = native.load(require=True)
+    for B in (1, 3):
+        for H, HKV in ((4, 2), (4, 4)):
+            for S in (256, 512):
+                sq = lib.attn_bwd_ws_bytes(B, H, HKV, S, causal)
+                rect = lib.attn_bwd_ws_bytes_rect(B, H, HKV, S, S, causal)
+                assert sq == rect, (B, H, HKV, S, causal)
+                # the knob forces the split: dk then dv partials [B,H,S,128]
+                assert sq == 2 * B * H * S * 128 * 4, (B, H, HKV, S, causal)
+            # S % 256 != 0 is not a block shape
+            assert lib.attn_bwd_ws_bytes(B, H, HKV, 128, causal) == 0
+            assert lib.attn_bwd_ws_bytes_rect(B, H, HKV, 128, 128, causal) == 0
+    # causal implies square
+    assert lib.attn_bwd_ws_bytes_rect(1, 4, 2, 256, 512, 1) == 0
+    assert lib.attn_bwd_ws_bytes_rect(1, 4, 2, 256, 512, 0) > 0

@@ -393,9 +393,12 @@ class FakeKubeApi(KubeApi):
             self._emit("MODIFIED", "pod", pod)
 
     def set_all_pods_phase(self, namespace: str, phase: str, **kw):
-        for (ns, name) in list(self.pods):
-            if ns == namespace:
-                self.set_pod_phase(ns, name, phase, **kw)
+        # one critical section (the lock is re-entrant): a controller thread
+        # may delete a pod between a snapshot of the names and the update
+        with self._lock:
+            for (ns, name) in list(self.pods):
+                if ns == namespace:
+                    self.set_pod_phase(ns, name, phase, **kw)
 
     def set_pod_log(self, namespace: str, name: str, text: str):
         with self._lock:

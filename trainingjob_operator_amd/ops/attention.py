@@ -370,63 +370,40 @@ def flash_attention_fwd_only(q, k, v, scale=None):
     return _run_fwd(q, k, v, scale)
 
 
-def flash_attention_fwd_nw8(q, k, v, scale=None):
-    """The 8-wave (BM=256) instantiation, kept callable for A/B."""
+def _fwd_entry(entry: str, q, k, v, scale=None, kv_heads_arg: bool = True):
+    """Call one forward A/B entry of the library by name -> (out, lse). Every
+    entry takes (batch, heads, kv heads, S); v5 has no GQA and no kv heads."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     B, H, S, D = q.shape
-    HKV = k.shape[1]
+    dims = (B, H, k.shape[1], S) if kv_heads_arg else (B, H, S)
     lib = native.load(require=True)
     out = torch.empty(B, H, S, D, dtype=torch.bfloat16, device=q.device)
     lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
-    rc = lib.attn_fwd_nw8(
+    rc = getattr(lib, entry)(
         native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
         out.data_ptr(), lse.data_ptr(),
         q.stride(0), q.stride(1), q.stride(2),
         k.stride(0), k.stride(1), k.stride(2),
         v.stride(0), v.stride(1), v.stride(2),
-        B, H, HKV, S, scale)
-    native.check_rc(rc, "attn_fwd_nw8", f"B={B} H={H} S={S}")
+        *dims, scale)
+    native.check_rc(rc, entry, f"B={B} H={H} S={S}")
     return out, lse
+
+
+def flash_attention_fwd_nw8(q, k, v, scale=None):
+    """The 8-wave (BM=256) instantiation, kept callable for A/B."""
+    return _fwd_entry("attn_fwd_nw8", q, k, v, scale)
 
 
 def flash_attention_fwd_v7(q, k, v, scale=None):
     """The 3-deep all-glds pipeline forward (A/B candidate)."""
-    if scale is None:
-        scale = 1.0 / math.sqrt(q.shape[-1])
-    B, H, S, D = q.shape
-    HKV = k.shape[1]
-    lib = native.load(require=True)
-    out = torch.empty(B, H, S, D, dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
-    rc = lib.attn_fwd_v7(
-        native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-        out.data_ptr(), lse.data_ptr(),
-        q.stride(0), q.stride(1), q.stride(2),
-        k.stride(0), k.stride(1), k.stride(2),
-        v.stride(0), v.stride(1), v.stride(2),
-        B, H, HKV, S, scale)
-    native.check_rc(rc, "attn_fwd_v7", f"B={B} H={H} S={S}")
-    return out, lse
+    return _fwd_entry("attn_fwd_v7", q, k, v, scale)
 
 
 def flash_attention_fwd_v5(q, k, v, scale=None):
     """The 4-wave v5 forward, kept callable for A/B benchmarking."""
-    if scale is None:
-        scale = 1.0 / math.sqrt(q.shape[-1])
-    B, H, S, D = q.shape
-    lib = native.load(require=True)
-    out = torch.empty(B, H, S, D, dtype=torch.bfloat16, device=q.device)
-    lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
-    rc = lib.attn_fwd_v5(
-        native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-        out.data_ptr(), lse.data_ptr(),
-        q.stride(0), q.stride(1), q.stride(2),
-        k.stride(0), k.stride(1), k.stride(2),
-        v.stride(0), v.stride(1), v.stride(2),
-        B, H, S, scale)
-    native.check_rc(rc, "attn_fwd_v5", f"B={B} H={H} S={S}")
-    return out, lse
+    return _fwd_entry("attn_fwd_v5", q, k, v, scale, kv_heads_arg=False)
 
 
 # ---------------------------------------------------------------------------

@@ -228,6 +228,222 @@ __host__ __device__ __forceinline__ int attn_pair_xch(int wid, int c) {
   return ((wid & 3) * 4 + c) * 64;
 }
 
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define V6_BM 256
+#define V6_QBLK 32
+#define V6_BN 64
+// per-buffer LDS halves (u16 counts): K [64][128] swizzled rows, then the
+// transposed V image (pitch 144 B + 256 B XOR tail)
+#define V6_K_U16 (V6_BN * ATTN_D)                        // 8192
+#define V6_V_U16 (ATTN_D * (VT_PITCH_B / 2) + 128)       // 9344
+#define V6_BUF_U16 (V6_K_U16 + V6_V_U16)
+
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
+// raw v_exp_f32 (2^x): libm exp2f lowers to a ~5-instruction guarded
+// sequence (ldexp + cndmask pairs); softmax arguments are <= 0 and
+// underflow-to-0 is exactly what we want.
+__device__ __forceinline__ float exp2_raw(float x) {
+  float r;
+  asm("v_exp_f32 %0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+
+// 3-deep glds pipeline helpers (fwd v7 + the v7-style backward kernels):
+// counted vmcnt only, raw barriers (no vmcnt(0) drain in any main loop)
+__device__ __forceinline__ void v7_wait_vmcnt4() {
+  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+}
+__device__ __forceinline__ void v7_wait_vmcnt0() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ void v7_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+}
+
+#define V7_RING 3
+
+// ---------------------------------------------------------------------------
+// Device pieces shared by the 32x32x16 kernels (v6/v7 forward, dq, dv, dk and
+// the pair kernels). All of them are lane-local in the owned row: lane
+// (low = lane & 31, hi = lane >> 5) holds C[(r & 3) + 8 * (r >> 2) + 4 * hi]
+// [low] in register r of an f32x16 accumulator.
+// ---------------------------------------------------------------------------
+
+#define ATTN_LOG2E 1.4426950408889634f
+
+// one 16-byte fragment: MFMA operand, global/LDS vector, packed bf16 pairs
+union AttnFrag { bf16x8 v; uint4 u; unsigned w[4]; u16 h[8]; };
+
+// T12 repack of the 8 values s[pb .. pb+7] (pb = 0 or 8) of a C tile into
+// the B fragment of its 16-row chunk: lane holds B[k = hi*8 + j][n = low]
+__device__ __forceinline__ bf16x8 attn_repack(f32x16 s, int pb) {
+  const unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
+  const unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
+  const unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
+  const unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
+  auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+  auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+  AttnFrag f;
+  f.w[0] = r02[0];
+  f.w[1] = r13[0];
+  f.w[2] = r02[1];
+  f.w[3] = r13[1];
+  return f.v;
+}
+
+// a lane's persistent row (Q, K, V or dO) as 8 k-chunk fragments: lane
+// holds row[kc*16 + hi*8 + j]
+__device__ __forceinline__ void attn_load_row(AttnFrag (&f)[8],
+                                              const u16* row, int hi) {
+#pragma unroll
+  for (int kc = 0; kc < 8; ++kc)
+    f[kc].u = *reinterpret_cast<const uint4*>(row + kc * 16 + hi * 8);
+}
+
+template <int N>
+__device__ __forceinline__ void attn_zero(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+
+// d subtile ds of a lane's row: bf16 to an output row, fp32 to a partial row
+__device__ __forceinline__ void attn_store_bf16(u16* row, const f32x16& acc,
+                                                int ds, int hi) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int d0 = 8 * g + 4 * hi + 32 * ds;
+    uint2 wv;
+    wv.x = cvt_pk_bf16(acc[4 * g + 0], acc[4 * g + 1]);
+    wv.y = cvt_pk_bf16(acc[4 * g + 2], acc[4 * g + 3]);
+    *reinterpret_cast<uint2*>(row + d0) = wv;
+  }
+}
+__device__ __forceinline__ void attn_store_f32(float* row, const f32x16& acc,
+                                               int ds, int hi) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int d0 = 8 * g + 4 * hi + 32 * ds;
+    float4 wv;
+    wv.x = acc[4 * g + 0];
+    wv.y = acc[4 * g + 1];
+    wv.z = acc[4 * g + 2];
+    wv.w = acc[4 * g + 3];
+    *reinterpret_cast<float4*>(row + d0) = wv;
+  }
+}
+
+// Staging by global->LDS DMA (glds) writes lane-linear (rule 21), so the T2
+// swizzle of a row image is inverted onto the SOURCE address: the 16 bytes
+// that land at lane-linear byte L of a k_byte image of rows row0 .. row0+63
+// come from here. The image stays byte-identical to a ds_write one and the
+// XOR only permutes 16-B slots inside one 256-B row (same coalescing).
+__device__ __forceinline__ const u16* attn_glds_src(const u16* base, int row0,
+                                                    int L, long ss) {
+  const int r = L >> 8;
+  const int in = (((L & 255) ^ ((r & 15) << 4)) >> 1);
+  return base + (long)(row0 + r) * ss + in;
+}
+
+// Issue a thread's two 16-byte glds for each of two 64-row images,
+// interleaved, and advance the sources one tile. A wave's 64 lanes land
+// contiguously at img + i * HALF + woff (u16, woff wave-uniform).
+template <int HALF>
+__device__ __forceinline__ void attn_glds_rows2(
+    u16* img_a, const u16* (&gp_a)[2], long step_a,
+    u16* img_b, const u16* (&gp_b)[2], long step_b, int woff) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    __builtin_amdgcn_global_load_lds((const u32*)gp_a[i],
+                                     (u32*)&img_a[i * HALF + woff], 16, 0, 0);
+    gp_a[i] += step_a;
+    __builtin_amdgcn_global_load_lds((const u32*)gp_b[i],
+                                     (u32*)&img_b[i * HALF + woff], 16, 0, 0);
+    gp_b[i] += step_b;
+  }
+}
+
+// Thread tid's share of a 64-row transposed (vt_byte) image: rows rp2 and
+// rp2 + 1, 8 columns from c8, written as 8 kv-pair words.
+__device__ __forceinline__ void attn_write_t(char* img, const uint4& row_a,
+                                             const uint4& row_b, int tid) {
+  const int rp2 = (tid >> 4) * 2;
+  const int c8 = (tid & 15) * 8;
+  union { uint4 u; u16 h[8]; } va, vb;
+  va.u = row_a;
+  vb.u = row_b;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const u32 pair = (u32)va.h[j] | ((u32)vb.h[j] << 16);
+    *reinterpret_cast<u32*>(&img[vt_byte(c8 + j, rp2)]) = pair;
+  }
+}
+// the same share, read back from a landed k_byte row image (LDS -> LDS)
+__device__ __forceinline__ void attn_transpose(const u16* rows, char* img,
+                                               int tid) {
+  const char* src = reinterpret_cast<const char*>(rows);
+  const int rp2 = (tid >> 4) * 2;
+  const int c8 = (tid & 15) * 8;
+  attn_write_t(img,
+               *reinterpret_cast<const uint4*>(&src[k_byte(rp2, c8)]),
+               *reinterpret_cast<const uint4*>(&src[k_byte(rp2 + 1, c8)]),
+               tid);
+}
+
+// LDS of the v7 forward and of dq: a 3-slot ring of K row images, a 3-slot
+// ring of V row images (both glds), then 2 transposed images built locally.
+// Slot addressing by arithmetic (pointer arrays spill under pressure).
+#define ATTN_RING_U16 (V7_RING * 2 * V6_K_U16 + 2 * V6_V_U16)
+__device__ __forceinline__ u16* attn_ring_k(u16* lds, int slot) {
+  return &lds[slot * V6_K_U16];
+}
+__device__ __forceinline__ u16* attn_ring_v(u16* lds, int slot) {
+  return &lds[(V7_RING + slot) * V6_K_U16];
+}
+__device__ __forceinline__ char* attn_ring_t(u16* lds, int p) {
+  return reinterpret_cast<char*>(&lds[2 * V7_RING * V6_K_U16]) +
+         p * (V6_V_U16 * 2);
+}
+
+// Ring sources of thread tid: wave w stages rows 8w..8w+7 - exactly the
+// rows its own lanes transpose, so the wave's own counted vmcnt covers them
+// (rows staged by another wave are only guaranteed landed after a barrier).
+struct AttnRingSrc {
+  const u16* kgp[2];
+  const u16* vgp[2];
+  long kstep, vstep;
+  int lslot;                                  // wave-uniform u16 base
+};
+__device__ __forceinline__ AttnRingSrc attn_ring_src(
+    const u16* kbase, long k_ss, const u16* vbase, long v_ss, int tid) {
+  AttnRingSrc s;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int L = (tid & ~63) * 32 + i * 1024 + (tid & 63) * 16;
+    s.kgp[i] = attn_glds_src(kbase, 0, L, k_ss);
+    s.vgp[i] = attn_glds_src(vbase, 0, L, v_ss);
+  }
+  s.kstep = (long)V6_BN * k_ss;
+  s.vstep = (long)V6_BN * v_ss;
+  s.lslot = (tid & ~63) * 16;
+  return s;
+}
+// issue the next K and V tiles into ring slot `slot`
+__device__ __forceinline__ void attn_ring_issue(u16* lds, int slot,
+                                                AttnRingSrc& s) {
+  attn_glds_rows2<512>(attn_ring_k(lds, slot), s.kgp, s.kstep,
+                       attn_ring_v(lds, slot), s.vgp, s.vstep, s.lslot);
+}
+
+
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ out,
@@ -412,48 +628,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 // qb launch order (longest blocks first), native GQA (kv head = h / group).
 // ===========================================================================
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define V6_BM 256
-#define V6_QBLK 32
-#define V6_BN 64
-// per-buffer LDS halves (u16 counts): K [64][128] swizzled rows, then the
-// transposed V image (pitch 144 B + 256 B XOR tail)
-#define V6_K_U16 (V6_BN * ATTN_D)                        // 8192
-#define V6_V_U16 (ATTN_D * (VT_PITCH_B / 2) + 128)       // 9344
-#define V6_BUF_U16 (V6_K_U16 + V6_V_U16)
-
-__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// raw v_exp_f32 (2^x): libm exp2f lowers to a ~5-instruction guarded
-// sequence (ldexp + cndmask pairs); softmax arguments are <= 0 and
-// underflow-to-0 is exactly what we want.
-__device__ __forceinline__ float exp2_raw(float x) {
-  float r;
-  asm("v_exp_f32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
-
-// 3-deep glds pipeline helpers (fwd v7 + the v7-style backward kernels):
-// counted vmcnt only, raw barriers (no vmcnt(0) drain in any main loop)
-__device__ __forceinline__ void v7_wait_vmcnt4() {
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-}
-__device__ __forceinline__ void v7_wait_vmcnt0() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-__device__ __forceinline__ void v7_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-#define V7_RING 3
-
-
 template <int NW>   // waves per workgroup: 4 (BM=128, 2 WGs/CU) or 8 (BM=256)
 __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -591,7 +765,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
     const bool need_mask = kv0 + V6_BN > q0w;
 
     f32x16 s0, s1;
-    union PF { bf16x8 v; unsigned u[4]; } pa[4];
+    AttnFrag pa[4];
     float pm = -INFINITY;
     if (active) {
       // ---- S^T = K @ Q^T over 2 kv-subtiles of 32 ----
@@ -667,6 +841,9 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
       for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
+          // kept inline here: through attn_repack this kernel's <4>
+          // instantiation measured 1.3 % slower
+          // (profiles/r09_attention_refactor.md)
           const int pb = cc * 8;
           unsigned a0, b0, a1, b1;
           if (sub == 0) {
@@ -682,11 +859,11 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
           }
           auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
           auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-          PF f;
-          f.u[0] = r02[0];
-          f.u[1] = r13[0];
-          f.u[2] = r02[1];
-          f.u[3] = r13[1];
+          AttnFrag f;
+          f.w[0] = r02[0];
+          f.w[1] = r13[0];
+          f.w[2] = r02[1];
+          f.w[3] = r13[1];
           pa[sub * 2 + cc] = f;
         }
       }
@@ -729,6 +906,35 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
     lse[((long)b * n_heads + h) * S + qrow] =
         m_run * 0.6931471805599453f + __logf(l_run);
 }
+#undef V6_GLDS_K
+#undef V6_LOAD_V
+#undef V6_WRITE_V
+
+// ===========================================================================
+// v7 forward: v6's math with a 3-deep ALL-glds staging pipeline.
+//
+// v6 parks ~49% of wave cycles at waits/barriers: its __syncthreads()
+// carries a vmcnt(0) drain (glds in flight) and the V register staging
+// serializes a global-load wait into the middle of every tile. v7:
+//   * K AND row-major V arrive by glds into a 3-slot ring (issue runs two
+//     tiles ahead; nothing in the main loop ever waits vmcnt(0));
+//   * the transposed V image is built LDS->LDS (2 b128 reads + 8 paired
+//     b32 writes per thread) from the landed row image — no global
+//     staging registers at all;
+//   * barriers are RAW s_barrier (guide: "3-buffer glds + raw barrier,
+//     counted vmcnt only"), one per tile, at tile end, guarding ring
+//     reuse and publishing the next transposed image. The transpose
+//     itself needs no barrier: every wave stages by glds exactly the
+//     rows it transposes, so its own counted vmcnt covers them.
+//
+// CAUSAL (also on the dq/dv/dk kernels): true is the causal kernel, tiles
+// up to the diagonal, mask on the diagonal band. false compiles the bound,
+// the tile skip and the mask out: every q block visits all S_kv/64 kv tiles,
+// for the blocks of ring attention that lie wholly below the diagonal. Those
+// may be rectangular: the non-causal kernels take the q length S and the k/v
+// length S_kv apart, the causal ones never read S_kv (S_q == S_kv == S).
+// Pipeline, ring depth, waits and barriers are shared.
+// ===========================================================================
 
 template <bool CAUSAL>
 __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
@@ -740,153 +946,176 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long v_sb, long v_sh, long v_ss,
     long o_sb, long o_sh, long o_ss,
     int n_heads, int gqa_group, int S, float scale2, int batch, int sched,
-    int S_kv);
-
-// The kernels move 16-byte vectors along D, so every stride must keep rows
-// 16-byte aligned (a multiple of 8 bf16 elements).
-static inline bool attn_strides_ok(const long* st, int n) {
-  for (int i = 0; i < n; ++i)
-    if (st[i] < 0 || st[i] % 8 != 0) return false;
-  return true;
-}
-
-// Schedule of one launch. AITJ_ATTN_SCHED=legacy|balanced forces every
-// kernel to that decode (read on every call, so both can be timed
-// alternately in one process); unset or anything else takes the default.
-static int attn_sched_mode() {
-  const char* e = std::getenv("AITJ_ATTN_SCHED");
-  if (e && std::strcmp(e, "legacy") == 0) return ATTN_SCHED_LEGACY;
-  return ATTN_SCHED_BALANCED;
-}
-
-// Host-callable decode (tests/test_attention_sched_cpu.py). sched: 0 legacy,
-// 1 balanced. Returns nonzero for an id outside the grid.
-extern "C" int attn_sched_decode(int sched, int id, int n_row_blocks,
-                                 int n_heads, int batch, int* rank,
-                                 int* head, int* b) {
-  if (n_row_blocks <= 0 || n_heads <= 0 || batch <= 0 || id < 0 ||
-      (long)id >= (long)n_row_blocks * n_heads * batch ||
-      (sched != ATTN_SCHED_LEGACY && sched != ATTN_SCHED_BALANCED))
-    return -1;
-  const AttnBlock blk = attn_sched_block((unsigned)id, (unsigned)n_row_blocks,
-                                         (unsigned)n_heads, (unsigned)batch,
+    int S_kv) {
+  // S is the q length: row blocks, qb, the lse row base. S_kv, the k/v
+  // length of a rectangular block, is read by the non-causal kernel alone.
+  constexpr int NT = 512;
+  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
                                          sched);
-  *rank = blk.rank;
-  *head = blk.head;
-  *b = blk.batch;
-  return 0;
-}
+  const int qb = S / 256 - 1 - blk.rank;   // longest-running blocks first
+  const int h = blk.head;
+  const int b = blk.batch;
+  const int hkv = h / gqa_group;
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
+  const int low = lane & 31;
+  const int hi = lane >> 5;
 
-// 1-D grid of the four scheduled kernels; the launchers refuse shapes
-// whose workgroup count does not fit an int
-static inline bool attn_grid_ok(int S, int n_heads, int batch) {
-  return (long)(S / 256) * n_heads * batch <= 0x7fffffffL;
-}
+  // ring: K rows (swizzled image) + V rows (swizzled image), both glds;
+  // 2 transposed-V images built locally
+  __shared__ __attribute__((aligned(16))) u16 lds[ATTN_RING_U16];
 
-// v7 launch shared by attn_fwd, attn_fwd_v7 (contiguous [B,H,S,D] out) and
-// attn_fwd_strided (out through batch/head/row strides)
-static int launch_fwd_v7(void* stream, const void* q, const void* k,
-                          const void* v, void* out, void* lse,
-                          long q_sb, long q_sh, long q_ss,
-                          long k_sb, long k_sh, long k_ss,
-                          long v_sb, long v_sh, long v_ss,
-                          long o_sb, long o_sh, long o_ss,
-                          int batch, int n_heads, int n_kv_heads, int S,
-                          float scale, bool causal = true, int S_kv = 0) {
-  // S_kv: k/v rows of a rectangular non-causal block; 0 = square
-  if (S_kv == 0) S_kv = S;
-  if (!attn_grid_ok(S, n_heads, batch) || (causal && S_kv != S)) return -1;
-  const float scale2 = scale * 1.4426950408889634f;   // fold log2(e)
-  dim3 grid((S / 256) * n_heads * batch), block(512);
-  hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<true>
-                            : attn_fwd_v7_kernel<false>, grid, block, 0,
-                     reinterpret_cast<hipStream_t>(stream),
-                     (const u16*)q, (const u16*)k, (const u16*)v,
-                     (u16*)out, (float*)lse, q_sb, q_sh, q_ss,
-                     k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
-                     o_sb, o_sh, o_ss, n_heads,
-                     n_heads / n_kv_heads, S, scale2, batch,
-                     attn_sched_mode(), S_kv);
-  return 0;
-}
+  const int q0w = qb * 256 + wid * 32;
+  const int qrow = q0w + low;
 
-extern "C" int attn_fwd(void* stream, const void* q, const void* k,
-                        const void* v, void* out, void* lse,
-                        long q_sb, long q_sh, long q_ss,
-                        long k_sb, long k_sh, long k_ss,
-                        long v_sb, long v_sh, long v_ss,
-                        int batch, int n_heads, int n_kv_heads, int S,
-                        float scale) {
-  if (S <= 0 || n_heads <= 0 || batch <= 0 || n_kv_heads <= 0 ||
-      n_heads % n_kv_heads != 0)
-    return -1;
-  if (S % 128 == 0) {
-    // BM=256 preferred: halves the K/V staging traffic vs BM=128 (each kv
-    // tile is read by half as many workgroups); measured 344 vs 587 us at
-    // B1H32S4096. BM=128 covers the S%128 shapes.
-    const float scale2 = scale * 1.4426950408889634f;   // fold log2(e)
-    if (S % 256 == 0) {
-      // v7: 3-deep all-glds pipeline, single raw barrier per tile
-      // (299 us vs v6's 346 at B1H32S4096; aotriton 425)
-      return launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
-                           k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
-                           (long)n_heads * S * ATTN_D, (long)S * ATTN_D,
-                           ATTN_D, batch, n_heads, n_kv_heads, S, scale);
+  AttnFrag qf[8];
+  attn_load_row(qf, q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss,
+                hi);
+
+  f32x16 oacc[4];
+  attn_zero(oacc);
+  float m_run = -INFINITY, l_run = 0.f;
+
+  // causal: tiles up to the diagonal; non-causal: every kv tile
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
+
+  // glds source pointers (swizzle-inverted, advanced per issue)
+  AttnRingSrc src = attn_ring_src(k + (long)b * k_sb + (long)hkv * k_sh, k_ss,
+                                  v + (long)b * v_sb + (long)hkv * v_sh, v_ss,
+                                  tid);
+
+  // prologue: issue tiles 0 and 1; build Vt[0] once tile 0 lands (LDS->LDS
+  // transpose of the landed V row image)
+  attn_ring_issue(lds, 0, src);
+  if (n_tiles > 1) attn_ring_issue(lds, 1, src);
+  if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
+  v7_barrier();
+  attn_transpose(attn_ring_v(lds, 0), attn_ring_t(lds, 0), tid);
+  // tile 0's PV reads every wave's share of Vt[0] before the first in-loop
+  // barrier (that one sits at the END of tile 0), so publish it here
+  v7_barrier();
+
+  for (int t = 0; t < n_tiles; ++t) {
+    const int kv0 = t * V6_BN;
+    const bool have2 = (t + 2) < n_tiles;
+    if (have2) attn_ring_issue(lds, (t + 2) % V7_RING, src);
+
+    char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
+    char* vtb = attn_ring_t(lds, t & 1);
+    const bool active = !CAUSAL || kv0 <= q0w + 31;
+    const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
+
+    f32x16 s0, s1;
+    AttnFrag pa[4];
+    float pm = -INFINITY;
+    if (active) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+#pragma unroll
+      for (int kc = 0; kc < 8; ++kc) {
+        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
+            &kb[k_byte(low, kc * 16 + hi * 8)]);
+        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kc].v, s0, 0, 0, 0);
+        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
+            &kb[k_byte(32 + low, kc * 16 + hi * 8)]);
+        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kc].v, s1, 0, 0, 0);
+      }
+      if (need_mask) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          float x0 = s0[r] * scale2;
+          if (kvr > qrow) x0 = -1e30f;
+          s0[r] = x0;
+          float x1 = s1[r] * scale2;
+          if (kvr + 32 > qrow) x1 = -1e30f;
+          s1[r] = x1;
+          pm = fmaxf(pm, fmaxf(x0, x1));
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          s0[r] *= scale2;
+          s1[r] *= scale2;
+          pm = fmaxf(pm, fmaxf(s0[r], s1[r]));
+        }
+      }
+      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
+
+      if (!__all(pm - m_run <= 8.0f)) {
+        const float mn = fmaxf(m_run, pm);
+        const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
+        m_run = mn;
+        l_run *= alpha;
+#pragma unroll
+        for (int ds = 0; ds < 4; ++ds)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;
+      }
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p0 = exp2_raw(s0[r] - m_run);
+        const float p1 = exp2_raw(s1[r] - m_run);
+        s0[r] = p0;
+        s1[r] = p1;
+        psum += p0 + p1;
+      }
+      psum += __shfl_xor(psum, 32, 64);
+      l_run += psum;
+
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+          pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);
+        }
+      }
+
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int ds = 0; ds < 4; ++ds) {
+          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
+              &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
+          oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              vf, pa[c].v, oacc[ds], 0, 0, 0);
+        }
+      }
     }
-    dim3 grid(S / 128, n_heads, batch), block(256);
-    hipLaunchKernelGGL((attn_fwd_v6_kernel<4>), grid, block, 0,
-                       reinterpret_cast<hipStream_t>(stream),
-                       (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
-                       (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                       v_sb, v_sh, v_ss, n_heads, n_heads / n_kv_heads, S,
-                       scale2);
-    return 0;
+    // end-of-tile: wait slot t+1 (counted — t+2 stays in flight), build
+    // the NEXT transposed image (different Vt buffer than this tile's PV
+    // reads, so it needs no pre-barrier), then ONE raw barrier guarding
+    // ring reuse + Vt visibility for tile t+1
+    if (t + 1 < n_tiles) {
+      if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
+      attn_transpose(attn_ring_v(lds, (t + 1) % V7_RING),
+                     attn_ring_t(lds, (t + 1) & 1), tid);
+    }
+    v7_barrier();
   }
-  if (S % ATTN_BM != 0 || n_kv_heads != n_heads) return -1;  // v5: no GQA
-  dim3 grid(S / ATTN_BM, n_heads, batch), block(256);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0,
-                     reinterpret_cast<hipStream_t>(stream),
-                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
-                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                     v_sb, v_sh, v_ss, n_heads, S, scale);
-  return 0;
-}
 
-// 8-wave instantiation kept callable for A/B benchmarking
-extern "C" int attn_fwd_nw8(void* stream, const void* q, const void* k,
-                            const void* v, void* out, void* lse,
-                            long q_sb, long q_sh, long q_ss,
-                            long k_sb, long k_sh, long k_ss,
-                            long v_sb, long v_sh, long v_ss,
-                            int batch, int n_heads, int n_kv_heads, int S,
-                            float scale) {
-  if (S <= 0 || S % 256 != 0 || n_heads % n_kv_heads != 0) return -1;
-  dim3 grid(S / 256, n_heads, batch), block(512);
-  const float scale2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL((attn_fwd_v6_kernel<8>), grid, block, 0,
-                     reinterpret_cast<hipStream_t>(stream),
-                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
-                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                     v_sb, v_sh, v_ss, n_heads, n_heads / n_kv_heads, S,
-                     scale2);
-  return 0;
-}
-
-// v5 kept callable for A/B benchmarking (scripts/attnbench.py v5)
-extern "C" int attn_fwd_v5(void* stream, const void* q, const void* k,
-                           const void* v, void* out, void* lse,
-                           long q_sb, long q_sh, long q_ss,
-                           long k_sb, long k_sh, long k_ss,
-                           long v_sb, long v_sh, long v_ss,
-                           int batch, int n_heads, int S, float scale) {
-  if (S <= 0 || S % ATTN_BM != 0 || n_heads <= 0 || batch <= 0) return -1;
-  dim3 grid(S / ATTN_BM, n_heads, batch), block(256);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0,
-                     reinterpret_cast<hipStream_t>(stream),
-                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
-                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                     v_sb, v_sh, v_ss, n_heads, S, scale);
-  return 0;
+  const float inv_l = 1.0f / l_run;
+  u16* orow = out + (long)b * o_sb + (long)h * o_sh + (long)qrow * o_ss;
+#pragma unroll
+  for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d0 = 8 * g + 4 * hi + 32 * ds;
+      const unsigned w0 = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
+                                      oacc[ds][4 * g + 1] * inv_l);
+      const unsigned w1 = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
+                                      oacc[ds][4 * g + 3] * inv_l);
+      uint2 wv;
+      wv.x = w0;
+      wv.y = w1;
+      *reinterpret_cast<uint2*>(orow + d0) = wv;
+    }
+  }
+  if (hi == 0)
+    lse[((long)b * n_heads + h) * S + qrow] =
+        m_run * 0.6931471805599453f + __logf(l_run);
 }
 
 // ===========================================================================
@@ -978,108 +1207,52 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const int lane = tid & 63;
   const int low = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * 1.4426950408889634f;
+  const float scale2 = scale * ATTN_LOG2E;
 
-  __shared__ __attribute__((aligned(16))) u16
-      lds[V7_RING * 2 * V6_K_U16 + 2 * V6_V_U16];
-#define DQ_K(SLOT) (&lds[(SLOT) * V6_K_U16])
-#define DQ_VR(SLOT) (&lds[(V7_RING + (SLOT)) * V6_K_U16])
-#define DQ_KT(P) (reinterpret_cast<char*>(&lds[2 * V7_RING * V6_K_U16]) \
-                  + (P) * (V6_V_U16 * 2))
+  // the ring holds K and V rows; the transposed images are K^T
+  __shared__ __attribute__((aligned(16))) u16 lds[ATTN_RING_U16];
 
   const int q0w = qb * 256 + wid * 32;
   const int qrow = q0w + low;
 
-  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
-  const u16* qptr = q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss;
-  const u16* doptr = dout + (long)b * do_sb + (long)h * do_sh
-                     + (long)qrow * do_ss;
-  F8 qf[8], dof[8];
-#pragma unroll
-  for (int kc = 0; kc < 8; ++kc) {
-    qf[kc].u = *reinterpret_cast<const uint4*>(qptr + kc * 16 + hi * 8);
-    dof[kc].u = *reinterpret_cast<const uint4*>(doptr + kc * 16 + hi * 8);
-  }
+  AttnFrag qf[8], dof[8];
+  attn_load_row(qf, q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss,
+                hi);
+  attn_load_row(dof, dout + (long)b * do_sb + (long)h * do_sh
+                         + (long)qrow * do_ss, hi);
   const long lrow = ((long)b * n_heads + h) * S + qrow;
-  const float lse2 = lse[lrow] * 1.4426950408889634f;
+  const float lse2 = lse[lrow] * ATTN_LOG2E;
   const float dlt = delta[lrow];
 
   f32x16 dqacc[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dqacc[ds][r] = 0.f;
+  attn_zero(dqacc);
 
-  const u16* kbase = k + (long)b * k_sb + (long)hkv * k_sh;
-  const u16* vbase = v + (long)b * v_sb + (long)hkv * v_sh;
   // causal: tiles up to the diagonal; non-causal: every kv tile
   const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
 
-  const u16* kgp[2];
-  const u16* vgp[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    // wave w stages rows 8w..8w+7 — exactly the rows its own lanes
-    // transpose below, so the wave's own counted vmcnt covers them (rows
-    // staged by another wave are only guaranteed landed after a barrier)
-    const int L = (tid & ~63) * 32 + i * 1024 + (tid & 63) * 16;
-    const int kr = L >> 8;
-    const int kin = (((L & 255) ^ ((kr & 15) << 4)) >> 1);
-    kgp[i] = kbase + (long)kr * k_ss + kin;
-    vgp[i] = vbase + (long)kr * v_ss + kin;
-  }
-  const long kstep = (long)V6_BN * k_ss;
-  const long vstep = (long)V6_BN * v_ss;
-  const int lslot = (tid & ~63) * 16;
+  AttnRingSrc src = attn_ring_src(k + (long)b * k_sb + (long)hkv * k_sh, k_ss,
+                                  v + (long)b * v_sb + (long)hkv * v_sh, v_ss,
+                                  tid);
 
-#define DQ_GLDS(SLOT)                                                       \
-  _Pragma("unroll")                                                         \
-  for (int i = 0; i < 2; ++i) {                                             \
-    __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)kgp[i], (u32*)&DQ_K(SLOT)[i * 512 + lslot],          \
-        16, 0, 0);                                                          \
-    kgp[i] += kstep;                                                        \
-    __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)vgp[i], (u32*)&DQ_VR(SLOT)[i * 512 + lslot],         \
-        16, 0, 0);                                                          \
-    vgp[i] += vstep;                                                        \
-  }
-
-  const int t_rp2 = (tid >> 4) * 2;
-  const int t_c8 = (tid & 15) * 8;
-#define DQ_TRANSPOSE(SRCSLOT, DST)                                          \
-  {                                                                         \
-    const char* srcb = reinterpret_cast<const char*>(DQ_K(SRCSLOT));        \
-    union { uint4 u4; u16 h[8]; } va_, vb_;                                 \
-    va_.u4 = *reinterpret_cast<const uint4*>(&srcb[k_byte(t_rp2, t_c8)]);   \
-    vb_.u4 = *reinterpret_cast<const uint4*>(                               \
-        &srcb[k_byte(t_rp2 + 1, t_c8)]);                                    \
-    _Pragma("unroll")                                                       \
-    for (int j = 0; j < 8; ++j) {                                           \
-      const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);              \
-      *reinterpret_cast<u32*>(&(DST)[vt_byte(t_c8 + j, t_rp2)]) = pair_;    \
-    }                                                                       \
-  }
-
-  DQ_GLDS(0)
-  if (n_tiles > 1) DQ_GLDS(1)
+  attn_ring_issue(lds, 0, src);
+  if (n_tiles > 1) attn_ring_issue(lds, 1, src);
   if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
   v7_barrier();
-  DQ_TRANSPOSE(0, DQ_KT(0))
+  attn_transpose(attn_ring_k(lds, 0), attn_ring_t(lds, 0), tid);
   v7_barrier();   // tile 0 reads every wave's share of KT[0]
 
   for (int t = 0; t < n_tiles; ++t) {
     const int kv0 = t * V6_BN;
     const bool have2 = (t + 2) < n_tiles;
-    if (have2) DQ_GLDS((t + 2) % V7_RING)
+    if (have2) attn_ring_issue(lds, (t + 2) % V7_RING, src);
 
-    char* kb = reinterpret_cast<char*>(DQ_K(t % V7_RING));
-    char* vb = reinterpret_cast<char*>(DQ_VR(t % V7_RING));
-    char* ktb = DQ_KT(t & 1);
+    char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
+    char* vb = reinterpret_cast<char*>(attn_ring_v(lds, t % V7_RING));
+    char* ktb = attn_ring_t(lds, t & 1);
     const bool active = !CAUSAL || kv0 <= q0w + 31;
     const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
 
-    union PF { bf16x8 v; unsigned u[4]; } pds[4];
+    AttnFrag pds[4];
     if (active) {
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
@@ -1108,21 +1281,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
           sx[r] = p * (dp[r] - dlt) * scale;
         }
 #pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          const int pb = cc * 8;
-          unsigned a0 = cvt_pk_bf16(sx[pb + 0], sx[pb + 1]);
-          unsigned b0 = cvt_pk_bf16(sx[pb + 4], sx[pb + 5]);
-          unsigned a1 = cvt_pk_bf16(sx[pb + 2], sx[pb + 3]);
-          unsigned b1 = cvt_pk_bf16(sx[pb + 6], sx[pb + 7]);
-          auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-          auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-          PF f;
-          f.u[0] = r02[0];
-          f.u[1] = r13[0];
-          f.u[2] = r02[1];
-          f.u[3] = r13[1];
-          pds[sub * 2 + cc] = f;
-        }
+        for (int cc = 0; cc < 2; ++cc)
+          pds[sub * 2 + cc].v = attn_repack(sx, cc * 8);
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -1137,27 +1297,15 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     }
     if (t + 1 < n_tiles) {
       if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
-      DQ_TRANSPOSE((t + 1) % V7_RING, DQ_KT((t + 1) & 1))
+      attn_transpose(attn_ring_k(lds, (t + 1) % V7_RING),
+                     attn_ring_t(lds, (t + 1) & 1), tid);
     }
     v7_barrier();
   }
 
   u16* dqrow = dq + (long)b * dq_sb + (long)h * dq_sh + (long)qrow * dq_ss;
 #pragma unroll
-  for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 8 * g + 4 * hi + 32 * ds;
-      const unsigned w0 = cvt_pk_bf16(dqacc[ds][4 * g + 0],
-                                      dqacc[ds][4 * g + 1]);
-      const unsigned w1 = cvt_pk_bf16(dqacc[ds][4 * g + 2],
-                                      dqacc[ds][4 * g + 3]);
-      uint2 wv;
-      wv.x = w0;
-      wv.y = w1;
-      *reinterpret_cast<uint2*>(dqrow + d0) = wv;
-    }
-  }
+  for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dqrow, dqacc[ds], ds, hi);
 }
 
 // ---------------------------------------------------------------------------
@@ -1173,7 +1321,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 #define BV_DOT_U16 (ATTN_D * (VT_PITCH_B / 2) + 128)
 #define BV_LSE_U16 128                      // 64 f32
 #define BV_BUF_U16 (BV_Q_U16 + BV_DOT_U16 + BV_LSE_U16)
-
 template <bool CAUSAL, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -1206,7 +1353,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   const int lane = tid & 63;
   const int low = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * 1.4426950408889634f;
+  const float scale2 = scale * ATTN_LOG2E;
 
   __shared__ __attribute__((aligned(16))) u16 lds[2][BV_BUF_U16];
   char* lds0 = reinterpret_cast<char*>(&lds[0][0]);
@@ -1222,18 +1369,14 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   const int kvrow = kv0w + low;              // this lane's kv row
 
   // K row in registers (persistent across the whole WG lifetime)
-  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
   const u16* kptr = k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
-  F8 kf[8];
+  AttnFrag kf[8];
 #pragma unroll
   for (int kc = 0; kc < 8; ++kc)
     kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
 
   f32x16 dvacc[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dvacc[ds][r] = 0.f;
+  attn_zero(dvacc);
 
   const int qt0 = CAUSAL ? strips.qt0 : 0;   // first q tile that sees us
   const int qtn = S / 64;
@@ -1281,7 +1424,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
       if (tid < 64)                                                         \
         *reinterpret_cast<float*>(                                          \
             &lds[BUFI][LSEOFF / 2 + tid * 2]) =                             \
-            lbase[(QT) * 64 + tid] * 1.4426950408889634f;                   \
+            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
     }
 #define BV_WRITE_DOT(BUF)                                                   \
     {                                                                       \
@@ -1314,7 +1457,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
       const bool active = !CAUSAL || qt * 64 + 63 >= kv0w;
       const bool need_mask = CAUSAL && qt * 64 < kv0w + 32;
 
-      union PF { bf16x8 v; unsigned u[4]; } pf[4];
+      AttnFrag pf[4];
       if (active) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
@@ -1339,19 +1482,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
           // repack P (C[q][kv]) -> B-fragments [k=q chunk][n=kv]
 #pragma unroll
           for (int cc = 0; cc < 2; ++cc) {
-            const int pb = cc * 8;
-            unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
-            unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
-            unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
-            unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
-            auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-            auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-            PF f;
-            f.u[0] = r02[0];
-            f.u[1] = r13[0];
-            f.u[2] = r02[1];
-            f.u[3] = r13[1];
-            pf[sub * 2 + cc] = f;
+            pf[sub * 2 + cc].v = attn_repack(s, cc * 8);
           }
         }
       }
@@ -1382,38 +1513,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     float* wrow =
         ws + (((long)b * n_heads + blk.head) * S_kv + kvrow) * ATTN_D;
 #pragma unroll
-    for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = 8 * g + 4 * hi + 32 * ds;
-        float4 wv;
-        wv.x = dvacc[ds][4 * g + 0];
-        wv.y = dvacc[ds][4 * g + 1];
-        wv.z = dvacc[ds][4 * g + 2];
-        wv.w = dvacc[ds][4 * g + 3];
-        *reinterpret_cast<float4*>(wrow + d0) = wv;
-      }
-    }
+    for (int ds = 0; ds < 4; ++ds) attn_store_f32(wrow, dvacc[ds], ds, hi);
     return;
   }
   // epilogue: dv rows through (batch, kv head, row) strides
   u16* dvrow = dv + (long)b * dv_sb + (long)hkv * dv_sh + (long)kvrow * dv_ss;
 #pragma unroll
-  for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 8 * g + 4 * hi + 32 * ds;
-      const unsigned w0 = cvt_pk_bf16(dvacc[ds][4 * g + 0],
-                                      dvacc[ds][4 * g + 1]);
-      const unsigned w1 = cvt_pk_bf16(dvacc[ds][4 * g + 2],
-                                      dvacc[ds][4 * g + 3]);
-      uint2 wv;
-      wv.x = w0;
-      wv.y = w1;
-      *reinterpret_cast<uint2*>(dvrow + d0) = wv;
-    }
-  }
+  for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dvrow, dvacc[ds], ds, hi);
 }
+#undef BV_STAGE_IN
+#undef BV_WRITE_DOT
 
 // ---------------------------------------------------------------------------
 // dK kernel: same kv-block walk as dV.
@@ -1430,7 +1539,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #define BK_LSE_U16 128
 #define BK_DLT_U16 128
 #define BK_BUF_U16 (BK_Q_U16 + BK_DO_U16 + BK_QT_U16 + BK_LSE_U16 + BK_DLT_U16)
-
 template <bool CAUSAL, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -1461,7 +1569,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   const int lane = tid & 63;
   const int low = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * 1.4426950408889634f;
+  const float scale2 = scale * ATTN_LOG2E;
 
   __shared__ __attribute__((aligned(16))) u16 lds[2][BK_BUF_U16];
   char* lds0 = reinterpret_cast<char*>(&lds[0][0]);
@@ -1477,10 +1585,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;
 
-  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
   const u16* kptr = k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
   const u16* vptr = v + (long)b * v_sb + (long)hkv * v_sh + (long)kvrow * v_ss;
-  F8 kf[8], vf[8];
+  AttnFrag kf[8], vf[8];
 #pragma unroll
   for (int kc = 0; kc < 8; ++kc) {
     kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
@@ -1488,10 +1595,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   }
 
   f32x16 dkacc[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dkacc[ds][r] = 0.f;
+  attn_zero(dkacc);
 
   const int qt0 = CAUSAL ? strips.qt0 : 0;
   const int qtn = S / 64;
@@ -1546,7 +1650,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
       qtp[1] += qstep;                                                      \
       if (tid < 64)                                                         \
         *reinterpret_cast<float*>(&lds[BUFI][LSEOFF / 2 + tid * 2]) =       \
-            lbase[(QT) * 64 + tid] * 1.4426950408889634f;                   \
+            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
       else if (tid < 128)                                                   \
         *reinterpret_cast<float*>(                                          \
             &lds[BUFI][DLTOFF / 2 + (tid - 64) * 2]) =                      \
@@ -1584,7 +1688,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
       const bool active = !CAUSAL || qt * 64 + 63 >= kv0w;
       const bool need_mask = CAUSAL && qt * 64 < kv0w + 32;
 
-      union PF { bf16x8 v; unsigned u[4]; } pf[4];
+      AttnFrag pf[4];
       if (active) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
@@ -1612,19 +1716,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
           }
 #pragma unroll
           for (int cc = 0; cc < 2; ++cc) {
-            const int pb = cc * 8;
-            unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
-            unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
-            unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
-            unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
-            auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-            auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-            PF f;
-            f.u[0] = r02[0];
-            f.u[1] = r13[0];
-            f.u[2] = r02[1];
-            f.u[3] = r13[1];
-            pf[sub * 2 + cc] = f;
+            pf[sub * 2 + cc].v = attn_repack(s, cc * 8);
           }
         }
       }
@@ -1654,37 +1746,15 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     float* wrow =
         ws + (((long)b * n_heads + blk.head) * S_kv + kvrow) * ATTN_D;
 #pragma unroll
-    for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = 8 * g + 4 * hi + 32 * ds;
-        float4 wv;
-        wv.x = dkacc[ds][4 * g + 0];
-        wv.y = dkacc[ds][4 * g + 1];
-        wv.z = dkacc[ds][4 * g + 2];
-        wv.w = dkacc[ds][4 * g + 3];
-        *reinterpret_cast<float4*>(wrow + d0) = wv;
-      }
-    }
+    for (int ds = 0; ds < 4; ++ds) attn_store_f32(wrow, dkacc[ds], ds, hi);
     return;
   }
   u16* dkrow = dk + (long)b * dk_sb + (long)hkv * dk_sh + (long)kvrow * dk_ss;
 #pragma unroll
-  for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 8 * g + 4 * hi + 32 * ds;
-      const unsigned w0 = cvt_pk_bf16(dkacc[ds][4 * g + 0],
-                                      dkacc[ds][4 * g + 1]);
-      const unsigned w1 = cvt_pk_bf16(dkacc[ds][4 * g + 2],
-                                      dkacc[ds][4 * g + 3]);
-      uint2 wv;
-      wv.x = w0;
-      wv.y = w1;
-      *reinterpret_cast<uint2*>(dkrow + d0) = wv;
-    }
-  }
+  for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dkrow, dkacc[ds], ds, hi);
 }
+#undef BK_STAGE_IN
+#undef BK_WRITE_QT
 
 // ---------------------------------------------------------------------------
 // dV and dK with PAIR ownership (attn_bwd_pair): causal, unsplit. Same grid,
@@ -1725,7 +1795,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
   const int lane = tid & 63;
   const int low = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * 1.4426950408889634f;
+  const float scale2 = scale * ATTN_LOG2E;
 
   __shared__ __attribute__((aligned(16))) u16 lds[2][BV_BUF_U16];
   __shared__ __attribute__((aligned(16))) uint4 xch[ATTN_PAIR_XCH_U4];
@@ -1736,7 +1806,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
 
   const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
   uint4 dtst[2];
 
 #pragma unroll 1
@@ -1749,16 +1818,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
 
     const u16* kptr =
         k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
-    F8 kf[8];
+    AttnFrag kf[8];
 #pragma unroll
     for (int kc = 0; kc < 8; ++kc)
       kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
 
     f32x16 dvacc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dvacc[j][r] = 0.f;
+  attn_zero(dvacc);
 
     const int qt0 = pr.qt0;
 
@@ -1786,6 +1852,42 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
       const long qstep = (long)64 * q_ss;
       const long dostep = (long)64 * do_ss;
 
+// the staging of attn_bwd_dv_kernel, repeated: as shared functions it changed
+// the instruction stream of all four dv/dk kernels and cost this one 1 %
+// (profiles/r09_attention_refactor.md)
+#define BV_STAGE_IN(BUFI, QT)                                               \
+    {                                                                       \
+      _Pragma("unroll")                                                     \
+      for (int i = 0; i < 2; ++i) {                                         \
+        __builtin_amdgcn_global_load_lds(                                   \
+            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
+            16, 0, 0);                                                      \
+        qgp[i] += qstep;                                                    \
+      }                                                                     \
+      dtst[0] = *reinterpret_cast<const uint4*>(dtp[0]);                    \
+      dtst[1] = *reinterpret_cast<const uint4*>(dtp[1]);                    \
+      dtp[0] += dostep;                                                     \
+      dtp[1] += dostep;                                                     \
+      if (tid < 64)                                                         \
+        *reinterpret_cast<float*>(                                          \
+            &lds[BUFI][LSEOFF / 2 + tid * 2]) =                             \
+            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
+    }
+#define BV_WRITE_DOT(BUF)                                                   \
+    {                                                                       \
+      const int rp2_ = (tid >> 4) * 2;                                      \
+      const int c8_ = (tid & 15) * 8;                                       \
+      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
+      va_.u4 = dtst[0];                                                     \
+      vb_.u4 = dtst[1];                                                     \
+      _Pragma("unroll")                                                     \
+      for (int j = 0; j < 8; ++j) {                                         \
+        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
+        *reinterpret_cast<u32*>(&(BUF)[DOTOFF + vt_byte(c8_ + j, rp2_)]) =  \
+            pair_;                                                          \
+      }                                                                     \
+    }
+
       BV_STAGE_IN(0, qt0)
       BV_WRITE_DOT(lds0)
       __syncthreads();
@@ -1801,7 +1903,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
         const bool active = qt * 64 + 63 >= kv0w;
         const bool need_mask = qt * 64 < kv0w + 32;
 
-        union PF { bf16x8 v; unsigned u[4]; uint4 q4; } pf[4];
+        AttnFrag pf[4];
         if (active) {
           f32x16 s;
 #pragma unroll
@@ -1825,26 +1927,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
           // 2*sub and 2*sub + 1, into the exchange area
 #pragma unroll
           for (int cc = 0; cc < 2; ++cc) {
-            const int pb = cc * 8;
-            unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
-            unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
-            unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
-            unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
-            auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-            auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-            PF f;
-            f.u[0] = r02[0];
-            f.u[1] = r13[0];
-            f.u[2] = r02[1];
-            f.u[3] = r13[1];
-            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.q4;
+            AttnFrag f;
+            f.v = attn_repack(s, cc * 8);
+            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.u;
           }
         }
         v7_barrier();                        // fragments of both subs written
         if (active) {
 #pragma unroll
           for (int c = 0; c < 4; ++c)
-            pf[c].q4 = xch[attn_pair_xch(wu64, c) + lane];
+            pf[c].u = xch[attn_pair_xch(wu64, c) + lane];
         }
         if (have_next) {
           char* nb = cur ? lds0 : lds1;
@@ -1888,6 +1980,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
     }
   }
 }
+#undef BV_STAGE_IN
+#undef BV_WRITE_DOT
 
 __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -1910,7 +2004,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
   const int lane = tid & 63;
   const int low = lane & 31;
   const int hi = lane >> 5;
-  const float scale2 = scale * 1.4426950408889634f;
+  const float scale2 = scale * ATTN_LOG2E;
 
   __shared__ __attribute__((aligned(16))) u16 lds[2][BK_BUF_U16];
   __shared__ __attribute__((aligned(16))) uint4 xch[ATTN_PAIR_XCH_U4];
@@ -1923,7 +2017,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
 
   const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
   uint4 qtst[2];
 
 #pragma unroll 1
@@ -1938,7 +2031,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
         k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
     const u16* vptr =
         v + (long)b * v_sb + (long)hkv * v_sh + (long)kvrow * v_ss;
-    F8 kf[8], vf[8];
+    AttnFrag kf[8], vf[8];
 #pragma unroll
     for (int kc = 0; kc < 8; ++kc) {
       kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
@@ -1946,10 +2039,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
     }
 
     f32x16 dkacc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dkacc[j][r] = 0.f;
+  attn_zero(dkacc);
 
     const int qt0 = pr.qt0;
 
@@ -1981,6 +2071,50 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
       const long qstep = (long)64 * q_ss;
       const long dostep = (long)64 * do_ss;
 
+// the staging of attn_bwd_dk_kernel, repeated: as shared functions it changed
+// the instruction stream of all four dv/dk kernels and cost this one 1 %
+// (profiles/r09_attention_refactor.md)
+#define BK_STAGE_IN(BUFI, QT)                                               \
+    {                                                                       \
+      _Pragma("unroll")                                                     \
+      for (int i = 0; i < 2; ++i) {                                         \
+        __builtin_amdgcn_global_load_lds(                                   \
+            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
+            16, 0, 0);                                                      \
+        qgp[i] += qstep;                                                    \
+        __builtin_amdgcn_global_load_lds(                                   \
+            (const u32*)dgp[i],                                             \
+            (u32*)&lds[BUFI][DOOFF / 2 + (i * 512 + wu64 * 64) * 8],        \
+            16, 0, 0);                                                      \
+        dgp[i] += dostep;                                                   \
+      }                                                                     \
+      qtst[0] = *reinterpret_cast<const uint4*>(qtp[0]);                    \
+      qtst[1] = *reinterpret_cast<const uint4*>(qtp[1]);                    \
+      qtp[0] += qstep;                                                      \
+      qtp[1] += qstep;                                                      \
+      if (tid < 64)                                                         \
+        *reinterpret_cast<float*>(&lds[BUFI][LSEOFF / 2 + tid * 2]) =       \
+            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
+      else if (tid < 128)                                                   \
+        *reinterpret_cast<float*>(                                          \
+            &lds[BUFI][DLTOFF / 2 + (tid - 64) * 2]) =                      \
+            dbase[(QT) * 64 + tid - 64];                                    \
+    }
+#define BK_WRITE_QT(BUF)                                                    \
+    {                                                                       \
+      const int rp2_ = (tid >> 4) * 2;                                      \
+      const int c8_ = (tid & 15) * 8;                                       \
+      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
+      va_.u4 = qtst[0];                                                     \
+      vb_.u4 = qtst[1];                                                     \
+      _Pragma("unroll")                                                     \
+      for (int j = 0; j < 8; ++j) {                                         \
+        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
+        *reinterpret_cast<u32*>(&(BUF)[QTOFF + vt_byte(c8_ + j, rp2_)]) =   \
+            pair_;                                                          \
+      }                                                                     \
+    }
+
       BK_STAGE_IN(0, qt0)
       BK_WRITE_QT(lds0)
       __syncthreads();
@@ -1998,7 +2132,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
         const bool active = qt * 64 + 63 >= kv0w;
         const bool need_mask = qt * 64 < kv0w + 32;
 
-        union PF { bf16x8 v; unsigned u[4]; uint4 q4; } pf[4];
+        AttnFrag pf[4];
         if (active) {
           f32x16 s, dp;
 #pragma unroll
@@ -2024,26 +2158,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
           }
 #pragma unroll
           for (int cc = 0; cc < 2; ++cc) {
-            const int pb = cc * 8;
-            unsigned a0 = cvt_pk_bf16(s[pb + 0], s[pb + 1]);
-            unsigned b0 = cvt_pk_bf16(s[pb + 4], s[pb + 5]);
-            unsigned a1 = cvt_pk_bf16(s[pb + 2], s[pb + 3]);
-            unsigned b1 = cvt_pk_bf16(s[pb + 6], s[pb + 7]);
-            auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-            auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-            PF f;
-            f.u[0] = r02[0];
-            f.u[1] = r13[0];
-            f.u[2] = r02[1];
-            f.u[3] = r13[1];
-            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.q4;
+            AttnFrag f;
+            f.v = attn_repack(s, cc * 8);
+            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.u;
           }
         }
         v7_barrier();                        // fragments of both subs written
         if (active) {
 #pragma unroll
           for (int c = 0; c < 4; ++c)
-            pf[c].q4 = xch[attn_pair_xch(wu64, c) + lane];
+            pf[c].u = xch[attn_pair_xch(wu64, c) + lane];
         }
         if (have_next) {
           char* nb = cur ? lds0 : lds1;
@@ -2085,28 +2209,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
     }
   }
 }
-
-// ---------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------
-
-// batch / head / row strides of one [B, heads, S, 128] operand (elements)
-struct AttnStride { long sb, sh, ss; };
-
-static inline AttnStride attn_dense_stride(int n_heads, int S) {
-  return {(long)n_heads * S * ATTN_D, (long)S * ATTN_D, (long)ATTN_D};
-}
-
-// delta[q] = rowsum(dO[q] * O[q]); delta is always dense [B,H,S] fp32
-static void launch_delta(hipStream_t st, const void* out, const void* dout,
-                         void* delta, AttnStride os, AttnStride dos,
-                         int batch, int n_heads, int S) {
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(S / 16, n_heads, batch),
-                     dim3(256), 0, st,
-                     (const u16*)dout, (const u16*)out, (float*)delta,
-                     dos.sb, dos.sh, dos.ss, os.sb, os.sh, os.ss,
-                     n_heads, S);
-}
+#undef BK_STAGE_IN
+#undef BK_WRITE_QT
 
 // ---------------------------------------------------------------------------
 // Split dK/dV: sum the gqa_group fp32 partials of each kv head in fixed
@@ -2151,6 +2255,232 @@ __global__ __launch_bounds__(256) void attn_bwd_reduce_kernel(
       ? dv + bi * dv_sb + (long)hkv * dv_sh + (long)s * dv_ss
       : dk + bi * dk_sb + (long)hkv * dk_sh + (long)s * dk_ss;
   *reinterpret_cast<uint4*>(dst + sub * 8) = o;
+}
+
+// ---------------------------------------------------------------------------
+// attn_merge: fold one block result (o_blk bf16, lse_blk) into the running
+// fp32 accumulator (o_acc, lse_acc), in place:
+//   lse_new = logaddexp(lse_acc, lse_blk)
+//   o_acc   = o_acc * exp(lse_acc - lse_new) + o_blk * exp(lse_blk - lse_new)
+// One 16-lane group per row, 8 elements per lane (one 16-B bf16 load, two
+// 16-B fp32 loads and stores). The group's lane 0 alone reads and writes
+// the row's lse pair and hands the two weights to the other 15 lanes. The
+// weights go through the pair's max, so an accumulator at (0, -inf) takes
+// weight exactly 0 and the block weight exactly 1 (no -inf - -inf).
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void attn_merge_kernel(
+    float* __restrict__ o_acc, float* __restrict__ lse_acc,
+    const u16* __restrict__ o_blk, const float* __restrict__ lse_blk,
+    long ob_sb, long ob_sh, long ob_ss, int n_heads, int S, long n_rows) {
+  const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (row >= n_rows) return;          // whole 16-lane groups leave together
+  const int sub = threadIdx.x & 15;
+  float wa = 0.f, wb = 0.f;
+  if (sub == 0) {
+    const float la = lse_acc[row], lb = lse_blk[row];
+    const float m = fmaxf(la, lb);
+    if (m != -INFINITY) {
+      const float ea = __expf(la - m), eb = __expf(lb - m);
+      const float sum = ea + eb;
+      wa = ea / sum;
+      wb = eb / sum;
+      lse_acc[row] = m + __logf(sum);
+    }
+  }
+  wa = __shfl(wa, 0, 16);
+  wb = __shfl(wb, 0, 16);
+  const long bh = row / S;
+  const int s = (int)(row - bh * S);
+  const long bi = bh / n_heads;
+  const int h = (int)(bh - bi * n_heads);
+  union { uint4 u; u16 h[8]; } ob;
+  ob.u = *reinterpret_cast<const uint4*>(
+      o_blk + bi * ob_sb + (long)h * ob_sh + (long)s * ob_ss + sub * 8);
+  float4* acc = reinterpret_cast<float4*>(o_acc + row * ATTN_D + sub * 8);
+  float4 a0 = acc[0], a1 = acc[1];
+  a0.x = a0.x * wa + bf2f_(ob.h[0]) * wb;
+  a0.y = a0.y * wa + bf2f_(ob.h[1]) * wb;
+  a0.z = a0.z * wa + bf2f_(ob.h[2]) * wb;
+  a0.w = a0.w * wa + bf2f_(ob.h[3]) * wb;
+  a1.x = a1.x * wa + bf2f_(ob.h[4]) * wb;
+  a1.y = a1.y * wa + bf2f_(ob.h[5]) * wb;
+  a1.z = a1.z * wa + bf2f_(ob.h[6]) * wb;
+  a1.w = a1.w * wa + bf2f_(ob.h[7]) * wb;
+  acc[0] = a0;
+  acc[1] = a1;
+}
+
+// batch / head / row strides of one [B, heads, S, 128] operand (elements)
+struct AttnStride { long sb, sh, ss; };
+// the three strides as consecutive kernel arguments
+#define ATTN_S3(s) (s).sb, (s).sh, (s).ss
+
+static inline AttnStride attn_dense_stride(int n_heads, int S) {
+  return {(long)n_heads * S * ATTN_D, (long)S * ATTN_D, (long)ATTN_D};
+}
+
+// triple i of the host long[] the *_strided and block entries take
+static inline AttnStride attn_stride_at(const long* st, int i) {
+  return {st[3 * i], st[3 * i + 1], st[3 * i + 2]};
+}
+
+// The kernels move 16-byte vectors along D, so every stride must keep rows
+// 16-byte aligned (a multiple of 8 bf16 elements).
+static inline bool attn_strides_ok(const long* st, int n) {
+  for (int i = 0; i < n; ++i)
+    if (st[i] < 0 || st[i] % 8 != 0) return false;
+  return true;
+}
+
+// Schedule of one launch. AITJ_ATTN_SCHED=legacy|balanced forces every
+// kernel to that decode (read on every call, so both can be timed
+// alternately in one process); unset or anything else takes the default.
+static int attn_sched_mode() {
+  const char* e = std::getenv("AITJ_ATTN_SCHED");
+  if (e && std::strcmp(e, "legacy") == 0) return ATTN_SCHED_LEGACY;
+  return ATTN_SCHED_BALANCED;
+}
+
+// Host-callable decode (tests/test_attention_sched_cpu.py). sched: 0 legacy,
+// 1 balanced. Returns nonzero for an id outside the grid.
+extern "C" int attn_sched_decode(int sched, int id, int n_row_blocks,
+                                 int n_heads, int batch, int* rank,
+                                 int* head, int* b) {
+  if (n_row_blocks <= 0 || n_heads <= 0 || batch <= 0 || id < 0 ||
+      (long)id >= (long)n_row_blocks * n_heads * batch ||
+      (sched != ATTN_SCHED_LEGACY && sched != ATTN_SCHED_BALANCED))
+    return -1;
+  const AttnBlock blk = attn_sched_block((unsigned)id, (unsigned)n_row_blocks,
+                                         (unsigned)n_heads, (unsigned)batch,
+                                         sched);
+  *rank = blk.rank;
+  *head = blk.head;
+  *b = blk.batch;
+  return 0;
+}
+
+// 1-D grid of the four scheduled kernels; the launchers refuse shapes
+// whose workgroup count does not fit an int
+static inline bool attn_grid_ok(int S, int n_heads, int batch) {
+  return (long)(S / 256) * n_heads * batch <= 0x7fffffffL;
+}
+
+// v7 launch shared by attn_fwd, attn_fwd_v7 (contiguous [B,H,S,D] out) and
+// attn_fwd_strided (out through batch/head/row strides)
+static int launch_fwd_v7(void* stream, const void* q, const void* k,
+                          const void* v, void* out, void* lse,
+                          AttnStride qs, AttnStride ks, AttnStride vs,
+                          AttnStride os, int batch, int n_heads,
+                          int n_kv_heads, int S, float scale,
+                          bool causal = true, int S_kv = 0) {
+  // S_kv: k/v rows of a rectangular non-causal block; 0 = square
+  if (S_kv == 0) S_kv = S;
+  if (!attn_grid_ok(S, n_heads, batch) || (causal && S_kv != S)) return -1;
+  const float scale2 = scale * ATTN_LOG2E;   // fold log2(e)
+  dim3 grid((S / 256) * n_heads * batch), block(512);
+  hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<true>
+                            : attn_fwd_v7_kernel<false>, grid, block, 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     (const u16*)q, (const u16*)k, (const u16*)v,
+                     (u16*)out, (float*)lse, ATTN_S3(qs), ATTN_S3(ks),
+                     ATTN_S3(vs), ATTN_S3(os), n_heads,
+                     n_heads / n_kv_heads, S, scale2, batch,
+                     attn_sched_mode(), S_kv);
+  return 0;
+}
+
+extern "C" int attn_fwd(void* stream, const void* q, const void* k,
+                        const void* v, void* out, void* lse,
+                        long q_sb, long q_sh, long q_ss,
+                        long k_sb, long k_sh, long k_ss,
+                        long v_sb, long v_sh, long v_ss,
+                        int batch, int n_heads, int n_kv_heads, int S,
+                        float scale) {
+  if (S <= 0 || n_heads <= 0 || batch <= 0 || n_kv_heads <= 0 ||
+      n_heads % n_kv_heads != 0)
+    return -1;
+  if (S % 128 == 0) {
+    // BM=256 preferred: halves the K/V staging traffic vs BM=128 (each kv
+    // tile is read by half as many workgroups); measured 344 vs 587 us at
+    // B1H32S4096. BM=128 covers the S%128 shapes.
+    const float scale2 = scale * ATTN_LOG2E;   // fold log2(e)
+    if (S % 256 == 0) {
+      // v7: 3-deep all-glds pipeline, single raw barrier per tile
+      // (299 us vs v6's 346 at B1H32S4096; aotriton 425)
+      return launch_fwd_v7(stream, q, k, v, out, lse, {q_sb, q_sh, q_ss},
+                           {k_sb, k_sh, k_ss}, {v_sb, v_sh, v_ss},
+                           attn_dense_stride(n_heads, S), batch, n_heads,
+                           n_kv_heads, S, scale);
+    }
+    dim3 grid(S / 128, n_heads, batch), block(256);
+    hipLaunchKernelGGL((attn_fwd_v6_kernel<4>), grid, block, 0,
+                       reinterpret_cast<hipStream_t>(stream),
+                       (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
+                       (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
+                       v_sb, v_sh, v_ss, n_heads, n_heads / n_kv_heads, S,
+                       scale2);
+    return 0;
+  }
+  if (S % ATTN_BM != 0 || n_kv_heads != n_heads) return -1;  // v5: no GQA
+  dim3 grid(S / ATTN_BM, n_heads, batch), block(256);
+  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
+                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
+                     v_sb, v_sh, v_ss, n_heads, S, scale);
+  return 0;
+}
+
+// 8-wave instantiation kept callable for A/B benchmarking
+extern "C" int attn_fwd_nw8(void* stream, const void* q, const void* k,
+                            const void* v, void* out, void* lse,
+                            long q_sb, long q_sh, long q_ss,
+                            long k_sb, long k_sh, long k_ss,
+                            long v_sb, long v_sh, long v_ss,
+                            int batch, int n_heads, int n_kv_heads, int S,
+                            float scale) {
+  if (S <= 0 || S % 256 != 0 || n_heads % n_kv_heads != 0) return -1;
+  dim3 grid(S / 256, n_heads, batch), block(512);
+  const float scale2 = scale * ATTN_LOG2E;
+  hipLaunchKernelGGL((attn_fwd_v6_kernel<8>), grid, block, 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
+                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
+                     v_sb, v_sh, v_ss, n_heads, n_heads / n_kv_heads, S,
+                     scale2);
+  return 0;
+}
+
+// v5 kept callable for A/B benchmarking (scripts/attnbench.py v5)
+extern "C" int attn_fwd_v5(void* stream, const void* q, const void* k,
+                           const void* v, void* out, void* lse,
+                           long q_sb, long q_sh, long q_ss,
+                           long k_sb, long k_sh, long k_ss,
+                           long v_sb, long v_sh, long v_ss,
+                           int batch, int n_heads, int S, float scale) {
+  if (S <= 0 || S % ATTN_BM != 0 || n_heads <= 0 || batch <= 0) return -1;
+  dim3 grid(S / ATTN_BM, n_heads, batch), block(256);
+  hipLaunchKernelGGL(attn_fwd_kernel, grid, block, 0,
+                     reinterpret_cast<hipStream_t>(stream),
+                     (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
+                     (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
+                     v_sb, v_sh, v_ss, n_heads, S, scale);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------
+
+// delta[q] = rowsum(dO[q] * O[q]); delta is always dense [B,H,S] fp32
+static void launch_delta(hipStream_t st, const void* out, const void* dout,
+                         void* delta, AttnStride os, AttnStride dos,
+                         int batch, int n_heads, int S) {
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(S / 16, n_heads, batch),
+                     dim3(256), 0, st,
+                     (const u16*)dout, (const u16*)out, (float*)delta,
+                     ATTN_S3(dos), ATTN_S3(os), n_heads, S);
 }
 
 static inline bool attn_block_shape_ok(int batch, int n_heads,
@@ -2294,18 +2624,8 @@ extern "C" int attn_bwd_strips_decode(int fold, int rank, int wid,
   return 0;
 }
 
-// Bytes of fp32 workspace the backward of this shape needs right now (dk
-// partials [B,H,S,128] then dv partials); 0 = the unsplit path. Host only.
-extern "C" long attn_bwd_ws_bytes(int batch, int n_heads, int n_kv_heads,
-                                  int S, int causal) {
-  if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return 0;
-  if (!attn_bwd_use_split(batch, n_heads, n_kv_heads, S, causal != 0))
-    return 0;
-  return 2L * batch * n_heads * S * ATTN_D * (long)sizeof(float);
-}
-
-// A rectangular block: S_q query rows against S_kv key rows, each a multiple
-// of 256. Only non-causal blocks may be rectangular.
+// A block of S_q query rows against S_kv key rows, each a multiple of 256;
+// a square block is S_q == S_kv. Only non-causal blocks may be rectangular.
 static inline bool attn_rect_shape_ok(int batch, int n_heads, int n_kv_heads,
                                       int S_q, int S_kv, bool causal) {
   return attn_block_shape_ok(batch, n_heads, n_kv_heads, S_q) &&
@@ -2313,8 +2633,9 @@ static inline bool attn_rect_shape_ok(int batch, int n_heads, int n_kv_heads,
          !(causal && S_q != S_kv);
 }
 
-// attn_bwd_ws_bytes for an S_q x S_kv block: the partials are kv rows,
-// dk [B,H,S_kv,128] then dv, and the split rule counts kv workgroups.
+// Bytes of fp32 workspace the backward of an S_q x S_kv block needs right
+// now; 0 = the unsplit path. The partials are kv rows, dk [B,H,S_kv,128]
+// then dv, and the split rule counts kv workgroups. Host only.
 extern "C" long attn_bwd_ws_bytes_rect(int batch, int n_heads, int n_kv_heads,
                                        int S_q, int S_kv, int causal) {
   if (!attn_rect_shape_ok(batch, n_heads, n_kv_heads, S_q, S_kv, causal != 0))
@@ -2322,6 +2643,12 @@ extern "C" long attn_bwd_ws_bytes_rect(int batch, int n_heads, int n_kv_heads,
   if (!attn_bwd_use_split(batch, n_heads, n_kv_heads, S_kv, causal != 0))
     return 0;
   return 2L * batch * n_heads * S_kv * ATTN_D * (long)sizeof(float);
+}
+
+// the square case
+extern "C" long attn_bwd_ws_bytes(int batch, int n_heads, int n_kv_heads,
+                                  int S, int causal) {
+  return attn_bwd_ws_bytes_rect(batch, n_heads, n_kv_heads, S, S, causal);
 }
 
 // dq + dv + dk from given lse and delta (dense [B,H,S] fp32). ws != null
@@ -2345,9 +2672,9 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dq,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
-                       dqs.sb, dqs.sh, dqs.ss,
+                       ATTN_S3(qs), ATTN_S3(ks),
+                       ATTN_S3(vs), ATTN_S3(dos),
+                       ATTN_S3(dqs),
                        n_heads, n_heads / n_kv_heads, S, scale, batch, sched,
                        S_kv);
   }
@@ -2364,8 +2691,8 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
     hipLaunchKernelGGL(attn_bwd_dv_pair_kernel, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)dout,
                        (const float*)lse, (u16*)dv,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
+                       ATTN_S3(qs), ATTN_S3(ks),
+                       ATTN_S3(dos), ATTN_S3(dvs),
                        n_heads, n_kv_heads, S, scale, batch, sched);
   } else {
     auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
@@ -2373,8 +2700,8 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
     hipLaunchKernelGGL(dv_kernel, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)dout,
                        (const float*)lse, (u16*)dv,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       dos.sb, dos.sh, dos.ss, dvs.sb, dvs.sh, dvs.ss,
+                       ATTN_S3(qs), ATTN_S3(ks),
+                       ATTN_S3(dos), ATTN_S3(dvs),
                        n_heads, n_kv_heads, S, scale, ws_v, batch, sched,
                        fold_v, S_kv);
   }
@@ -2383,9 +2710,9 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dk,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
-                       dks.sb, dks.sh, dks.ss,
+                       ATTN_S3(qs), ATTN_S3(ks),
+                       ATTN_S3(vs), ATTN_S3(dos),
+                       ATTN_S3(dks),
                        n_heads, n_kv_heads, S, scale, batch, sched);
   } else {
     auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
@@ -2394,9 +2721,9 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dk,
-                       qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
-                       vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
-                       dks.sb, dks.sh, dks.ss,
+                       ATTN_S3(qs), ATTN_S3(ks),
+                       ATTN_S3(vs), ATTN_S3(dos),
+                       ATTN_S3(dks),
                        n_heads, n_kv_heads, S, scale, ws_k, batch, sched,
                        fold_k, S_kv);
   }
@@ -2405,8 +2732,8 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
     hipLaunchKernelGGL(attn_bwd_reduce_kernel,
                        dim3((unsigned)((n_rows + 15) / 16), 2), dim3(256), 0,
                        st, (const float*)ws_k, (const float*)ws_v,
-                       (u16*)dk, (u16*)dv, dks.sb, dks.sh, dks.ss,
-                       dvs.sb, dvs.sh, dvs.ss, n_heads, n_kv_heads, S_kv,
+                       (u16*)dk, (u16*)dv, ATTN_S3(dks),
+                       ATTN_S3(dvs), n_heads, n_kv_heads, S_kv,
                        n_rows);
   }
 }
@@ -2426,14 +2753,11 @@ struct AttnBwdArgs {
 // Shape check of one backward call and the workspace bytes it needs now:
 // -1 for a shape the kernels do not cover (rectangular needs non-causal).
 static long attn_bwd_need(const AttnBwdArgs& a) {
-  if (a.S_kv == 0 || a.S_kv == a.S) {
-    if (!attn_block_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S)) return -1;
-    return attn_bwd_ws_bytes(a.batch, a.n_heads, a.n_kv_heads, a.S, a.causal);
-  }
-  if (!attn_rect_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S, a.S_kv,
+  const int S_kv = a.S_kv ? a.S_kv : a.S;
+  if (!attn_rect_shape_ok(a.batch, a.n_heads, a.n_kv_heads, a.S, S_kv,
                           a.causal))
     return -1;
-  return attn_bwd_ws_bytes_rect(a.batch, a.n_heads, a.n_kv_heads, a.S, a.S_kv,
+  return attn_bwd_ws_bytes_rect(a.batch, a.n_heads, a.n_kv_heads, a.S, S_kv,
                                 a.causal);
 }
 
@@ -2482,19 +2806,31 @@ static int launch_bwd_transient(hipStream_t st, const AttnBwdArgs& a) {
   return rc;
 }
 
+// Every backward entry comes as a pair: X takes a transient workspace, X_ws
+// the caller's (attn_bwd_ws_bytes[_rect]; may be null when that is 0).
+struct AttnWs { bool given; void* ptr; long bytes; };
+static const AttnWs ATTN_WS_TRANSIENT = {false, nullptr, 0};
+
+static int launch_bwd(void* stream, const AttnBwdArgs& a, AttnWs ws) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return ws.given ? launch_bwd_ws(st, a, ws.ptr, ws.bytes)
+                  : launch_bwd_transient(st, a);
+}
+
 // out, dout, dq: dense [B,H,S,D]; dk, dv: dense [B,HKV,S,D]
-static AttnBwdArgs attn_bwd_dense_args(
-    const void* q, const void* k, const void* v, const void* out,
-    const void* dout, const void* lse, void* delta, void* dq, void* dk,
-    void* dv, long q_sb, long q_sh, long q_ss, long k_sb, long k_sh,
-    long k_ss, long v_sb, long v_sh, long v_ss, int batch, int n_heads,
-    int n_kv_heads, int S, float scale) {
+static int attn_bwd_dense(void* stream, const void* q, const void* k,
+                          const void* v, const void* out, const void* dout,
+                          const void* lse, void* delta, void* dq, void* dk,
+                          void* dv, AttnStride qs, AttnStride ks,
+                          AttnStride vs, int batch, int n_heads,
+                          int n_kv_heads, int S, float scale, AttnWs ws) {
   const AttnStride dh = attn_dense_stride(n_heads, S);
   const AttnStride dkv = attn_dense_stride(n_kv_heads, S);
-  return AttnBwdArgs{q, k, v, out, dout, lse, delta, dq, dk, dv,
-                     {q_sb, q_sh, q_ss}, {k_sb, k_sh, k_ss},
-                     {v_sb, v_sh, v_ss}, dh, dh, dh, dkv, dkv,
-                     batch, n_heads, n_kv_heads, S, scale, true, true};
+  return launch_bwd(stream,
+                    AttnBwdArgs{q, k, v, out, dout, lse, delta, dq, dk, dv,
+                                qs, ks, vs, dh, dh, dh, dkv, dkv, batch,
+                                n_heads, n_kv_heads, S, scale, true, true},
+                    ws);
 }
 
 extern "C" int attn_bwd(void* stream, const void* q, const void* k,
@@ -2506,16 +2842,12 @@ extern "C" int attn_bwd(void* stream, const void* q, const void* k,
                         long v_sb, long v_sh, long v_ss,
                         int batch, int n_heads, int n_kv_heads, int S,
                         float scale) {
-  return launch_bwd_transient(
-      reinterpret_cast<hipStream_t>(stream),
-      attn_bwd_dense_args(q, k, v, out, dout, lse, delta, dq, dk, dv,
-                          q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                          v_sb, v_sh, v_ss, batch, n_heads, n_kv_heads, S,
-                          scale));
+  return attn_bwd_dense(stream, q, k, v, out, dout, lse, delta, dq, dk, dv,
+                        {q_sb, q_sh, q_ss}, {k_sb, k_sh, k_ss},
+                        {v_sb, v_sh, v_ss}, batch, n_heads, n_kv_heads, S,
+                        scale, ATTN_WS_TRANSIENT);
 }
 
-// attn_bwd with the caller's workspace (attn_bwd_ws_bytes; may be null
-// when that is 0)
 extern "C" int attn_bwd_ws(void* stream, const void* q, const void* k,
                            const void* v, const void* out, const void* dout,
                            const void* lse, void* delta,
@@ -2525,32 +2857,31 @@ extern "C" int attn_bwd_ws(void* stream, const void* q, const void* k,
                            long v_sb, long v_sh, long v_ss,
                            int batch, int n_heads, int n_kv_heads, int S,
                            float scale, void* ws, long ws_bytes) {
-  return launch_bwd_ws(
-      reinterpret_cast<hipStream_t>(stream),
-      attn_bwd_dense_args(q, k, v, out, dout, lse, delta, dq, dk, dv,
-                          q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
-                          v_sb, v_sh, v_ss, batch, n_heads, n_kv_heads, S,
-                          scale),
-      ws, ws_bytes);
+  return attn_bwd_dense(stream, q, k, v, out, dout, lse, delta, dq, dk, dv,
+                        {q_sb, q_sh, q_ss}, {k_sb, k_sh, k_ss},
+                        {v_sb, v_sh, v_ss}, batch, n_heads, n_kv_heads, S,
+                        scale, {true, ws, ws_bytes});
 }
 
 // attn_bwd with batch/head/row strides for every [.,.,S,128] operand, so
 // the gradients can land in head ranges of one packed [B,S,(H+2HKV)*128]
 // buffer and dout can arrive as [B,S,H*128]. st: 8 stride triples in the
 // order q, k, v, out, dout, dq, dk, dv.
-static bool attn_bwd_strided_args(
-    AttnBwdArgs* a, const void* q, const void* k, const void* v,
+static int attn_bwd_strided_any(
+    void* stream, const void* q, const void* k, const void* v,
     const void* out, const void* dout, const void* lse, void* delta,
     void* dq, void* dk, void* dv, const long* st, int batch, int n_heads,
-    int n_kv_heads, int S, float scale) {
-  if (!st || !attn_strides_ok(st, 24)) return false;
-  auto tri = [st](int i) {
-    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
-  };
-  *a = AttnBwdArgs{q, k, v, out, dout, lse, delta, dq, dk, dv,
-                   tri(0), tri(1), tri(2), tri(3), tri(4), tri(5), tri(6),
-                   tri(7), batch, n_heads, n_kv_heads, S, scale, true, true};
-  return true;
+    int n_kv_heads, int S, float scale, AttnWs ws) {
+  if (!st || !attn_strides_ok(st, 24)) return -1;
+  return launch_bwd(
+      stream,
+      AttnBwdArgs{q, k, v, out, dout, lse, delta, dq, dk, dv,
+                  attn_stride_at(st, 0), attn_stride_at(st, 1),
+                  attn_stride_at(st, 2), attn_stride_at(st, 3),
+                  attn_stride_at(st, 4), attn_stride_at(st, 5),
+                  attn_stride_at(st, 6), attn_stride_at(st, 7), batch,
+                  n_heads, n_kv_heads, S, scale, true, true},
+      ws);
 }
 
 extern "C" int attn_bwd_strided(void* stream, const void* q, const void* k,
@@ -2559,11 +2890,9 @@ extern "C" int attn_bwd_strided(void* stream, const void* q, const void* k,
                                 void* delta, void* dq, void* dk, void* dv,
                                 const long* st, int batch, int n_heads,
                                 int n_kv_heads, int S, float scale) {
-  AttnBwdArgs a;
-  if (!attn_bwd_strided_args(&a, q, k, v, out, dout, lse, delta, dq, dk, dv,
-                             st, batch, n_heads, n_kv_heads, S, scale))
-    return -1;
-  return launch_bwd_transient(reinterpret_cast<hipStream_t>(stream), a);
+  return attn_bwd_strided_any(stream, q, k, v, out, dout, lse, delta, dq, dk,
+                              dv, st, batch, n_heads, n_kv_heads, S, scale,
+                              ATTN_WS_TRANSIENT);
 }
 
 extern "C" int attn_bwd_strided_ws(void* stream, const void* q, const void* k,
@@ -2573,295 +2902,9 @@ extern "C" int attn_bwd_strided_ws(void* stream, const void* q, const void* k,
                                    const long* st, int batch, int n_heads,
                                    int n_kv_heads, int S, float scale,
                                    void* ws, long ws_bytes) {
-  AttnBwdArgs a;
-  if (!attn_bwd_strided_args(&a, q, k, v, out, dout, lse, delta, dq, dk, dv,
-                             st, batch, n_heads, n_kv_heads, S, scale))
-    return -1;
-  return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
-                       ws_bytes);
-}
-
-// ===========================================================================
-// v7 forward: v6's math with a 3-deep ALL-glds staging pipeline.
-//
-// v6 parks ~49% of wave cycles at waits/barriers: its __syncthreads()
-// carries a vmcnt(0) drain (glds in flight) and the V register staging
-// serializes a global-load wait into the middle of every tile. v7:
-//   * K AND row-major V arrive by glds into a 3-slot ring (issue runs two
-//     tiles ahead; nothing in the main loop ever waits vmcnt(0));
-//   * the transposed V image is built LDS->LDS (2 b128 reads + 8 paired
-//     b32 writes per thread) from the landed row image — no global
-//     staging registers at all;
-//   * barriers are RAW s_barrier (guide: "3-buffer glds + raw barrier,
-//     counted vmcnt only"), one per tile, at tile end, guarding ring
-//     reuse and publishing the next transposed image. The transpose
-//     itself needs no barrier: every wave stages by glds exactly the
-//     rows it transposes, so its own counted vmcnt covers them.
-//
-// CAUSAL (also on the dq/dv/dk kernels): true is the causal kernel, tiles
-// up to the diagonal, mask on the diagonal band. false compiles the bound,
-// the tile skip and the mask out: every q block visits all S_kv/64 kv tiles,
-// for the blocks of ring attention that lie wholly below the diagonal. Those
-// may be rectangular: the non-causal kernels take the q length S and the k/v
-// length S_kv apart, the causal ones never read S_kv (S_q == S_kv == S).
-// Pipeline, ring depth, waits and barriers are shared.
-// ===========================================================================
-
-template <bool CAUSAL>
-__global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k,
-    const u16* __restrict__ v, u16* __restrict__ out,
-    float* __restrict__ lse,
-    long q_sb, long q_sh, long q_ss,
-    long k_sb, long k_sh, long k_ss,
-    long v_sb, long v_sh, long v_ss,
-    long o_sb, long o_sh, long o_ss,
-    int n_heads, int gqa_group, int S, float scale2, int batch, int sched,
-    int S_kv) {
-  // S is the q length: row blocks, qb, the lse row base. S_kv, the k/v
-  // length of a rectangular block, is read by the non-causal kernel alone.
-  constexpr int NT = 512;
-  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
-                                         sched);
-  const int qb = S / 256 - 1 - blk.rank;   // longest-running blocks first
-  const int h = blk.head;
-  const int b = blk.batch;
-  const int hkv = h / gqa_group;
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-  const int low = lane & 31;
-  const int hi = lane >> 5;
-
-  // ring: K rows (swizzled image) + V rows (swizzled image), both glds;
-  // 2 transposed-V images built locally
-  __shared__ __attribute__((aligned(16))) u16
-      lds[V7_RING * 2 * V6_K_U16 + 2 * V6_V_U16];
-  // slot addressing by arithmetic (pointer arrays spill under pressure)
-#define LDSK(SLOT) (&lds[(SLOT) * V6_K_U16])
-#define LDSVR(SLOT) (&lds[(V7_RING + (SLOT)) * V6_K_U16])
-#define LDSVT(P) (reinterpret_cast<char*>(&lds[2 * V7_RING * V6_K_U16]) \
-                  + (P) * (V6_V_U16 * 2))
-
-  const int q0w = qb * 256 + wid * 32;
-  const int qrow = q0w + low;
-
-  union F8 { bf16x8 v; uint4 u; u16 h[8]; };
-  const u16* qptr = q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss;
-  F8 qf[8];
-#pragma unroll
-  for (int kc = 0; kc < 8; ++kc)
-    qf[kc].u = *reinterpret_cast<const uint4*>(qptr + kc * 16 + hi * 8);
-
-  f32x16 oacc[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) oacc[ds][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-
-  const u16* kbase = k + (long)b * k_sb + (long)hkv * k_sh;
-  const u16* vbase = v + (long)b * v_sb + (long)hkv * v_sh;
-  // causal: tiles up to the diagonal; non-causal: every kv tile
-  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
-
-  // glds source pointers (swizzle-inverted, advanced per issue)
-  const u16* kgp[2];
-  const u16* vgp[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    // wave w stages rows 8w..8w+7 — exactly the rows its own lanes
-    // transpose below, so the wave's own counted vmcnt covers them (rows
-    // staged by another wave are only guaranteed landed after a barrier)
-    const int L = (tid & ~63) * 32 + i * 1024 + (tid & 63) * 16;
-    const int kr = L >> 8;
-    const int kin = (((L & 255) ^ ((kr & 15) << 4)) >> 1);
-    kgp[i] = kbase + (long)kr * k_ss + kin;
-    vgp[i] = vbase + (long)kr * v_ss + kin;
-  }
-  const long kstep = (long)V6_BN * k_ss;
-  const long vstep = (long)V6_BN * v_ss;
-  const int lslot = (tid & ~63) * 16;         // wave-uniform u16 base
-
-#define V7_GLDS(SLOT)                                                       \
-  _Pragma("unroll")                                                         \
-  for (int i = 0; i < 2; ++i) {                                             \
-    __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)kgp[i], (u32*)&LDSK(SLOT)[i * 512 + lslot],          \
-        16, 0, 0);                                                          \
-    kgp[i] += kstep;                                                        \
-    __builtin_amdgcn_global_load_lds(                                       \
-        (const u32*)vgp[i], (u32*)&LDSVR(SLOT)[i * 512 + lslot],         \
-        16, 0, 0);                                                          \
-    vgp[i] += vstep;                                                        \
-  }
-
-  // LDS->LDS transpose of one landed V row-image into a vt image
-  const int t_rp2 = (tid >> 4) * 2;
-  const int t_c8 = (tid & 15) * 8;
-#define V7_TRANSPOSE(SRCSLOT, DST)                                          \
-  {                                                                         \
-    const char* srcb = reinterpret_cast<const char*>(LDSVR(SRCSLOT));       \
-    union { uint4 u4; u16 h[8]; } va_, vb_;                                 \
-    va_.u4 = *reinterpret_cast<const uint4*>(&srcb[k_byte(t_rp2, t_c8)]);   \
-    vb_.u4 = *reinterpret_cast<const uint4*>(                               \
-        &srcb[k_byte(t_rp2 + 1, t_c8)]);                                    \
-    _Pragma("unroll")                                                       \
-    for (int j = 0; j < 8; ++j) {                                           \
-      const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);              \
-      *reinterpret_cast<u32*>(&(DST)[vt_byte(t_c8 + j, t_rp2)]) = pair_;    \
-    }                                                                       \
-  }
-
-  // prologue: issue tiles 0 and 1; build Vt[0] once tile 0 lands
-  V7_GLDS(0)
-  if (n_tiles > 1) V7_GLDS(1)
-  if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
-  v7_barrier();
-  V7_TRANSPOSE(0, LDSVT(0))
-  // tile 0's PV reads every wave's share of Vt[0] before the first in-loop
-  // barrier (that one sits at the END of tile 0), so publish it here
-  v7_barrier();
-
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kv0 = t * V6_BN;
-    const bool have2 = (t + 2) < n_tiles;
-    if (have2) V7_GLDS((t + 2) % V7_RING)
-
-    char* kb = reinterpret_cast<char*>(LDSK(t % V7_RING));
-    char* vtb = LDSVT(t & 1);
-    const bool active = !CAUSAL || kv0 <= q0w + 31;
-    const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
-
-    f32x16 s0, s1;
-    union PF { bf16x8 v; unsigned u[4]; } pa[4];
-    float pm = -INFINITY;
-    if (active) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-#pragma unroll
-      for (int kc = 0; kc < 8; ++kc) {
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(low, kc * 16 + hi * 8)]);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kc].v, s0, 0, 0, 0);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(32 + low, kc * 16 + hi * 8)]);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kc].v, s1, 0, 0, 0);
-      }
-      if (need_mask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          float x0 = s0[r] * scale2;
-          if (kvr > qrow) x0 = -1e30f;
-          s0[r] = x0;
-          float x1 = s1[r] * scale2;
-          if (kvr + 32 > qrow) x1 = -1e30f;
-          s1[r] = x1;
-          pm = fmaxf(pm, fmaxf(x0, x1));
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] *= scale2;
-          s1[r] *= scale2;
-          pm = fmaxf(pm, fmaxf(s0[r], s1[r]));
-        }
-      }
-      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
-
-      if (!__all(pm - m_run <= 8.0f)) {
-        const float mn = fmaxf(m_run, pm);
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
-        m_run = mn;
-        l_run *= alpha;
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;
-      }
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p0 = exp2_raw(s0[r] - m_run);
-        const float p1 = exp2_raw(s1[r] - m_run);
-        s0[r] = p0;
-        s1[r] = p1;
-        psum += p0 + p1;
-      }
-      psum += __shfl_xor(psum, 32, 64);
-      l_run += psum;
-
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          const int pb = cc * 8;
-          unsigned a0, b0, a1, b1;
-          if (sub == 0) {
-            a0 = cvt_pk_bf16(s0[pb + 0], s0[pb + 1]);
-            b0 = cvt_pk_bf16(s0[pb + 4], s0[pb + 5]);
-            a1 = cvt_pk_bf16(s0[pb + 2], s0[pb + 3]);
-            b1 = cvt_pk_bf16(s0[pb + 6], s0[pb + 7]);
-          } else {
-            a0 = cvt_pk_bf16(s1[pb + 0], s1[pb + 1]);
-            b0 = cvt_pk_bf16(s1[pb + 4], s1[pb + 5]);
-            a1 = cvt_pk_bf16(s1[pb + 2], s1[pb + 3]);
-            b1 = cvt_pk_bf16(s1[pb + 6], s1[pb + 7]);
-          }
-          auto r02 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-          auto r13 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-          PF f;
-          f.u[0] = r02[0];
-          f.u[1] = r13[0];
-          f.u[2] = r02[1];
-          f.u[3] = r13[1];
-          pa[sub * 2 + cc] = f;
-        }
-      }
-
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) {
-          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-              &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-          oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              vf, pa[c].v, oacc[ds], 0, 0, 0);
-        }
-      }
-    }
-    // end-of-tile: wait slot t+1 (counted — t+2 stays in flight), build
-    // the NEXT transposed image (different Vt buffer than this tile's PV
-    // reads, so it needs no pre-barrier), then ONE raw barrier guarding
-    // ring reuse + Vt visibility for tile t+1
-    if (t + 1 < n_tiles) {
-      if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
-      V7_TRANSPOSE((t + 1) % V7_RING, LDSVT((t + 1) & 1))
-    }
-    v7_barrier();
-  }
-
-  const float inv_l = 1.0f / l_run;
-  u16* orow = out + (long)b * o_sb + (long)h * o_sh + (long)qrow * o_ss;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 8 * g + 4 * hi + 32 * ds;
-      const unsigned w0 = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
-                                      oacc[ds][4 * g + 1] * inv_l);
-      const unsigned w1 = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
-                                      oacc[ds][4 * g + 3] * inv_l);
-      uint2 wv;
-      wv.x = w0;
-      wv.y = w1;
-      *reinterpret_cast<uint2*>(orow + d0) = wv;
-    }
-  }
-  if (hi == 0)
-    lse[((long)b * n_heads + h) * S + qrow] =
-        m_run * 0.6931471805599453f + __logf(l_run);
+  return attn_bwd_strided_any(stream, q, k, v, out, dout, lse, delta, dq, dk,
+                              dv, st, batch, n_heads, n_kv_heads, S, scale,
+                              {true, ws, ws_bytes});
 }
 
 extern "C" int attn_fwd_v7(void* stream, const void* q, const void* k,
@@ -2872,10 +2915,10 @@ extern "C" int attn_fwd_v7(void* stream, const void* q, const void* k,
                            int batch, int n_heads, int n_kv_heads, int S,
                            float scale) {
   if (S <= 0 || S % 256 != 0 || n_heads % n_kv_heads != 0) return -1;
-  return launch_fwd_v7(stream, q, k, v, out, lse, q_sb, q_sh, q_ss,
-                       k_sb, k_sh, k_ss, v_sb, v_sh, v_ss,
-                       (long)n_heads * S * ATTN_D, (long)S * ATTN_D, ATTN_D,
-                       batch, n_heads, n_kv_heads, S, scale);
+  return launch_fwd_v7(stream, q, k, v, out, lse, {q_sb, q_sh, q_ss},
+                       {k_sb, k_sh, k_ss}, {v_sb, v_sh, v_ss},
+                       attn_dense_stride(n_heads, S), batch, n_heads,
+                       n_kv_heads, S, scale);
 }
 
 // v7 forward with `out` through batch/head/row strides as well (lse stays
@@ -2888,9 +2931,10 @@ extern "C" int attn_fwd_strided(void* stream, const void* q, const void* k,
       n_kv_heads <= 0 || n_heads % n_kv_heads != 0)
     return -1;
   if (!st || !attn_strides_ok(st, 12)) return -1;
-  return launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
-                       st[3], st[4], st[5], st[6], st[7], st[8], st[9],
-                       st[10], st[11], batch, n_heads, n_kv_heads, S, scale);
+  return launch_fwd_v7(stream, q, k, v, out, lse, attn_stride_at(st, 0),
+                       attn_stride_at(st, 1), attn_stride_at(st, 2),
+                       attn_stride_at(st, 3), batch, n_heads, n_kv_heads, S,
+                       scale);
 }
 
 // ===========================================================================
@@ -2914,10 +2958,10 @@ extern "C" int attn_block_fwd(void* stream, const void* q, const void* k,
                               int causal) {
   if (!attn_block_shape_ok(batch, n_heads, n_kv_heads, S)) return -1;
   if (!st || !attn_strides_ok(st, 12)) return -1;
-  return launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
-                       st[3], st[4], st[5], st[6], st[7], st[8], st[9],
-                       st[10], st[11], batch, n_heads, n_kv_heads, S, scale,
-                       causal != 0);
+  return launch_fwd_v7(stream, q, k, v, out, lse, attn_stride_at(st, 0),
+                       attn_stride_at(st, 1), attn_stride_at(st, 2),
+                       attn_stride_at(st, 3), batch, n_heads, n_kv_heads, S,
+                       scale, causal != 0);
 }
 
 // st: 2 triples out, dout
@@ -2927,27 +2971,29 @@ extern "C" int attn_delta(void* stream, const void* out, const void* dout,
   if (S <= 0 || S % 16 != 0 || n_heads <= 0 || batch <= 0) return -1;
   if (!st || !attn_strides_ok(st, 6)) return -1;
   launch_delta(reinterpret_cast<hipStream_t>(stream), out, dout, delta,
-               {st[0], st[1], st[2]}, {st[3], st[4], st[5]},
-               batch, n_heads, S);
+               attn_stride_at(st, 0), attn_stride_at(st, 1), batch, n_heads,
+               S);
   return 0;
 }
 
-// st: 7 triples q, k, v, dout, dq, dk, dv
-static bool attn_block_bwd_args(
-    AttnBwdArgs* a, const void* q, const void* k, const void* v,
+// st: 7 triples q, k, v, dout, dq, dk, dv. S_kv: k/v rows of a rectangular
+// block, 0 = square.
+static int attn_block_bwd_any(
+    void* stream, const void* q, const void* k, const void* v,
     const void* dout, const void* lse, const void* delta, void* dq, void* dk,
     void* dv, const long* st, int batch, int n_heads, int n_kv_heads, int S,
-    float scale, int causal) {
-  if (!st || !attn_strides_ok(st, 21)) return false;
-  auto tri = [st](int i) {
-    return AttnStride{st[3 * i], st[3 * i + 1], st[3 * i + 2]};
-  };
+    int S_kv, float scale, int causal, AttnWs ws) {
+  if (!st || !attn_strides_ok(st, 21)) return -1;
   // delta is an input here: never written, no out operand
-  *a = AttnBwdArgs{q, k, v, nullptr, dout, lse, const_cast<void*>(delta),
-                   dq, dk, dv, tri(0), tri(1), tri(2), AttnStride{0, 0, 0},
-                   tri(3), tri(4), tri(5), tri(6), batch, n_heads,
-                   n_kv_heads, S, scale, causal != 0, false};
-  return true;
+  return launch_bwd(
+      stream,
+      AttnBwdArgs{q, k, v, nullptr, dout, lse, const_cast<void*>(delta), dq,
+                  dk, dv, attn_stride_at(st, 0), attn_stride_at(st, 1),
+                  attn_stride_at(st, 2), AttnStride{0, 0, 0},
+                  attn_stride_at(st, 3), attn_stride_at(st, 4),
+                  attn_stride_at(st, 5), attn_stride_at(st, 6), batch,
+                  n_heads, n_kv_heads, S, scale, causal != 0, false, S_kv},
+      ws);
 }
 
 extern "C" int attn_block_bwd(void* stream, const void* q, const void* k,
@@ -2957,11 +3003,9 @@ extern "C" int attn_block_bwd(void* stream, const void* q, const void* k,
                               const long* st, int batch, int n_heads,
                               int n_kv_heads, int S, float scale,
                               int causal) {
-  AttnBwdArgs a;
-  if (!attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
-                           batch, n_heads, n_kv_heads, S, scale, causal))
-    return -1;
-  return launch_bwd_transient(reinterpret_cast<hipStream_t>(stream), a);
+  return attn_block_bwd_any(stream, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                            batch, n_heads, n_kv_heads, S, 0, scale, causal,
+                            ATTN_WS_TRANSIENT);
 }
 
 extern "C" int attn_block_bwd_ws(void* stream, const void* q, const void* k,
@@ -2971,12 +3015,9 @@ extern "C" int attn_block_bwd_ws(void* stream, const void* q, const void* k,
                                  const long* st, int batch, int n_heads,
                                  int n_kv_heads, int S, float scale,
                                  int causal, void* ws, long ws_bytes) {
-  AttnBwdArgs a;
-  if (!attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
-                           batch, n_heads, n_kv_heads, S, scale, causal))
-    return -1;
-  return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
-                       ws_bytes);
+  return attn_block_bwd_any(stream, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                            batch, n_heads, n_kv_heads, S, 0, scale, causal,
+                            {true, ws, ws_bytes});
 }
 
 // Rectangular blocks: S_q query rows against S_kv key rows (each a multiple
@@ -2992,10 +3033,21 @@ extern "C" int attn_block_fwd_rect(void* stream, const void* q, const void* k,
   if (!attn_rect_shape_ok(batch, n_heads, n_kv_heads, S_q, S_kv, causal != 0))
     return -1;
   if (!st || !attn_strides_ok(st, 12)) return -1;
-  return launch_fwd_v7(stream, q, k, v, out, lse, st[0], st[1], st[2],
-                       st[3], st[4], st[5], st[6], st[7], st[8], st[9],
-                       st[10], st[11], batch, n_heads, n_kv_heads, S_q, scale,
-                       causal != 0, S_kv);
+  return launch_fwd_v7(stream, q, k, v, out, lse, attn_stride_at(st, 0),
+                       attn_stride_at(st, 1), attn_stride_at(st, 2),
+                       attn_stride_at(st, 3), batch, n_heads, n_kv_heads, S_q,
+                       scale, causal != 0, S_kv);
+}
+
+static int attn_block_bwd_rect_any(
+    void* stream, const void* q, const void* k, const void* v,
+    const void* dout, const void* lse, const void* delta, void* dq, void* dk,
+    void* dv, const long* st, int batch, int n_heads, int n_kv_heads,
+    int S_q, int S_kv, float scale, int causal, AttnWs ws) {
+  if (S_kv <= 0) return -1;              // 0 would mean square below
+  return attn_block_bwd_any(stream, q, k, v, dout, lse, delta, dq, dk, dv, st,
+                            batch, n_heads, n_kv_heads, S_q, S_kv, scale,
+                            causal, ws);
 }
 
 extern "C" int attn_block_bwd_rect(void* stream, const void* q, const void* k,
@@ -3005,13 +3057,9 @@ extern "C" int attn_block_bwd_rect(void* stream, const void* q, const void* k,
                                    const long* st, int batch, int n_heads,
                                    int n_kv_heads, int S_q, int S_kv,
                                    float scale, int causal) {
-  AttnBwdArgs a;
-  if (S_kv <= 0 ||
-      !attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
-                           batch, n_heads, n_kv_heads, S_q, scale, causal))
-    return -1;
-  a.S_kv = S_kv;
-  return launch_bwd_transient(reinterpret_cast<hipStream_t>(stream), a);
+  return attn_block_bwd_rect_any(stream, q, k, v, dout, lse, delta, dq, dk,
+                                 dv, st, batch, n_heads, n_kv_heads, S_q,
+                                 S_kv, scale, causal, ATTN_WS_TRANSIENT);
 }
 
 extern "C" int attn_block_bwd_rect_ws(void* stream, const void* q,
@@ -3022,68 +3070,9 @@ extern "C" int attn_block_bwd_rect_ws(void* stream, const void* q,
                                       int n_heads, int n_kv_heads, int S_q,
                                       int S_kv, float scale, int causal,
                                       void* ws, long ws_bytes) {
-  AttnBwdArgs a;
-  if (S_kv <= 0 ||
-      !attn_block_bwd_args(&a, q, k, v, dout, lse, delta, dq, dk, dv, st,
-                           batch, n_heads, n_kv_heads, S_q, scale, causal))
-    return -1;
-  a.S_kv = S_kv;
-  return launch_bwd_ws(reinterpret_cast<hipStream_t>(stream), a, ws,
-                       ws_bytes);
-}
-
-// ---------------------------------------------------------------------------
-// attn_merge: fold one block result (o_blk bf16, lse_blk) into the running
-// fp32 accumulator (o_acc, lse_acc), in place:
-//   lse_new = logaddexp(lse_acc, lse_blk)
-//   o_acc   = o_acc * exp(lse_acc - lse_new) + o_blk * exp(lse_blk - lse_new)
-// One 16-lane group per row, 8 elements per lane (one 16-B bf16 load, two
-// 16-B fp32 loads and stores). The group's lane 0 alone reads and writes
-// the row's lse pair and hands the two weights to the other 15 lanes. The
-// weights go through the pair's max, so an accumulator at (0, -inf) takes
-// weight exactly 0 and the block weight exactly 1 (no -inf - -inf).
-// ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void attn_merge_kernel(
-    float* __restrict__ o_acc, float* __restrict__ lse_acc,
-    const u16* __restrict__ o_blk, const float* __restrict__ lse_blk,
-    long ob_sb, long ob_sh, long ob_ss, int n_heads, int S, long n_rows) {
-  const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (row >= n_rows) return;          // whole 16-lane groups leave together
-  const int sub = threadIdx.x & 15;
-  float wa = 0.f, wb = 0.f;
-  if (sub == 0) {
-    const float la = lse_acc[row], lb = lse_blk[row];
-    const float m = fmaxf(la, lb);
-    if (m != -INFINITY) {
-      const float ea = __expf(la - m), eb = __expf(lb - m);
-      const float sum = ea + eb;
-      wa = ea / sum;
-      wb = eb / sum;
-      lse_acc[row] = m + __logf(sum);
-    }
-  }
-  wa = __shfl(wa, 0, 16);
-  wb = __shfl(wb, 0, 16);
-  const long bh = row / S;
-  const int s = (int)(row - bh * S);
-  const long bi = bh / n_heads;
-  const int h = (int)(bh - bi * n_heads);
-  union { uint4 u; u16 h[8]; } ob;
-  ob.u = *reinterpret_cast<const uint4*>(
-      o_blk + bi * ob_sb + (long)h * ob_sh + (long)s * ob_ss + sub * 8);
-  float4* acc = reinterpret_cast<float4*>(o_acc + row * ATTN_D + sub * 8);
-  float4 a0 = acc[0], a1 = acc[1];
-  a0.x = a0.x * wa + bf2f_(ob.h[0]) * wb;
-  a0.y = a0.y * wa + bf2f_(ob.h[1]) * wb;
-  a0.z = a0.z * wa + bf2f_(ob.h[2]) * wb;
-  a0.w = a0.w * wa + bf2f_(ob.h[3]) * wb;
-  a1.x = a1.x * wa + bf2f_(ob.h[4]) * wb;
-  a1.y = a1.y * wa + bf2f_(ob.h[5]) * wb;
-  a1.z = a1.z * wa + bf2f_(ob.h[6]) * wb;
-  a1.w = a1.w * wa + bf2f_(ob.h[7]) * wb;
-  acc[0] = a0;
-  acc[1] = a1;
+  return attn_block_bwd_rect_any(stream, q, k, v, dout, lse, delta, dq, dk,
+                                 dv, st, batch, n_heads, n_kv_heads, S_q,
+                                 S_kv, scale, causal, {true, ws, ws_bytes});
 }
 
 // o_acc fp32 dense [B,H,S,128]; lse_acc, lse_blk fp32 dense [B,H,S];
@@ -3103,3 +3092,5 @@ extern "C" int attn_merge(void* stream, void* o_acc, void* lse_acc,
                      n_heads, S, n_rows);
   return 0;
 }
+
+#undef ATTN_S3
