@@ -17,7 +17,7 @@ training container is opaque to it); this is worker-side capability.
 from __future__ import annotations
 
 import os
-from typing import Iterator, Tuple
+from typing import Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -29,10 +29,15 @@ class TokenFileDataset:
     """Random fixed-length windows over a flat token-id file."""
 
     def __init__(self, path: str, seq_len: int, micro_batch: int,
-                 dtype: str = "uint16", seed: int = 1234, rank: int = 0):
+                 dtype: str = "uint16", seed: int = 1234, rank: int = 0,
+                 eos_token: Optional[int] = None):
         if dtype not in DTYPES:
             raise ValueError(f"dtype {dtype!r} not in {sorted(DTYPES)}")
         self.path = path
+        # set: batches() also yields each window's document layout, cut
+        # after every eos_token (ops/docmask.py), for document-masked
+        # attention
+        self.eos_token = eos_token
         self.seq_len = seq_len
         self.micro_batch = micro_batch
         self.rank = rank
@@ -49,7 +54,9 @@ class TokenFileDataset:
 
     def batches(self, device=None) -> Iterator[
             Tuple[torch.Tensor, torch.Tensor]]:
-        """Infinite (tokens, targets) stream: [B, S] int64 on `device`."""
+        """Infinite (tokens, targets) stream: [B, S] int64 on `device`.
+        With eos_token set: (tokens, targets, bounds), bounds int32 [2,B,S]
+        from doc_bounds_from_eos(tokens, eos_token) on the same device."""
         g = torch.Generator().manual_seed(self.seed * 1000 + self.rank)
         need = self.seq_len + 1
         while True:
@@ -60,7 +67,14 @@ class TokenFileDataset:
             batch = torch.from_numpy(rows.astype(np.int64))
             if device is not None:
                 batch = batch.to(device, non_blocking=True)
-            yield batch[:, :-1].contiguous(), batch[:, 1:].contiguous()
+            tokens = batch[:, :-1].contiguous()
+            targets = batch[:, 1:].contiguous()
+            if self.eos_token is None:
+                yield tokens, targets
+            else:
+                from ..ops.docmask import doc_bounds_from_eos
+                yield tokens, targets, doc_bounds_from_eos(tokens,
+                                                           self.eos_token)
 
 
 def write_token_file(path: str, tokens, dtype: str = "uint16") -> str:
@@ -78,7 +92,10 @@ def make_batches(cfg, device, rank: int = 0):
             raise FileNotFoundError(cfg.data_path)
         ds = TokenFileDataset(cfg.data_path, cfg.seq_len, cfg.micro_batch,
                               dtype=getattr(cfg, "data_dtype", "uint16"),
-                              seed=cfg.seed, rank=rank)
+                              seed=cfg.seed, rank=rank,
+                              eos_token=(cfg.eos_token
+                                         if getattr(cfg, "doc_mask", False)
+                                         else None))
         return ds.batches(device)
     from ..training import synthetic_batches
     return synthetic_batches(cfg, device, rank)

@@ -45,8 +45,9 @@ def _evaluate(trainer, cfg, n_batches: int):
     total = 0.0
     with torch.no_grad():
         for _ in range(n_batches):
-            tokens, targets = next(data)
-            total += float(model(tokens, targets))
+            # (tokens, targets[, bounds]): the layout rides along under
+            # --doc-mask
+            total += float(model(*next(data)))
     if was_training:
         model.train()
     loss = total / max(n_batches, 1)
@@ -84,7 +85,8 @@ def _run_ps_mode(args) -> int:
     cfg = TrainConfig(model=args.model, micro_batch=args.micro_batch,
                       grad_accum=args.grad_accum, seq_len=args.seq_len,
                       lr=args.lr, clip_grad_norm=0.0,
-                      data_path=args.data_path, data_dtype=args.data_dtype)
+                      data_path=args.data_path, data_dtype=args.data_dtype,
+                      doc_mask=args.doc_mask, eos_token=args.eos_token)
     try:
         run_role(cfg, role, index, n_ps, n_workers, args.steps)
     finally:
@@ -136,9 +138,8 @@ def _maybe_reexec_torchrun(argv) -> bool:
     return True  # unreachable
 
 
-def main(argv=None) -> int:
-    if _maybe_reexec_torchrun(argv):
-        return 0
+def build_parser() -> argparse.ArgumentParser:
+    """The launcher's command line (defaults from the operator's env)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--steps", type=int, default=1000,
@@ -164,6 +165,12 @@ def main(argv=None) -> int:
     ap.add_argument("--data-dtype", choices=("uint16", "uint32"),
                     default=os.environ.get("TRAININGJOB_DATA_DTYPE",
                                            "uint16"))
+    ap.add_argument("--doc-mask", action="store_true",
+                    help="mask attention at document boundaries (needs "
+                         "--data-path and --eos-token; dense DP training "
+                         "only)")
+    ap.add_argument("--eos-token", type=int, default=-1,
+                    help="token id that ends a document, for --doc-mask")
     ap.add_argument("--tp", type=int, default=int(os.environ.get(
         "TRAININGJOB_TP_SIZE", "1")),
         help="tensor-parallel degree (world = dp x tp; tp ranks adjacent)")
@@ -224,7 +231,13 @@ def main(argv=None) -> int:
     ap.add_argument("--metrics-port", type=int, default=int(os.environ.get(
         "TRAININGJOB_METRICS_PORT", "0")),
         help="expose Prometheus worker metrics (tokens/s, step time, loss)")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    if _maybe_reexec_torchrun(argv):
+        return 0
+    args = build_parser().parse_args(argv)
 
     logging.basicConfig(
         level=logging.INFO,
@@ -273,7 +286,8 @@ def main(argv=None) -> int:
         vocab_parallel=args.vocab_parallel,
         data_path=args.data_path, data_dtype=args.data_dtype,
         warmup_steps=args.warmup_steps, lr_decay_steps=args.lr_decay_steps,
-        min_lr=args.min_lr)
+        min_lr=args.min_lr, doc_mask=args.doc_mask,
+        eos_token=args.eos_token)
     if args.pp > 1:
         assert not args.ep, \
             "--pp with a MoE model shards experts automatically: the " \

@@ -31,14 +31,49 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
-def _sdpa(q, k, v, enable_gqa=False, is_causal=True):
+def _sdpa_docs(q, k, v, doc_bounds, enable_gqa, backend):
+    """Document-masked attention off the packed path: the native document
+    kernels where they apply (auto|native), else SDPA under the dense
+    [B,1,S,S] mask of the layout, on the backend asked for.
+
+    Knobs under doc_bounds: AITJ_SDPA_BACKEND selects as on the causal path
+    (efficient and math take the dense mask; torch's flash backend accepts
+    no attn_mask and raises). AITJ_ATTN_PACKED=0, AITJ_ATTN_BWD=aten and
+    AITJ_DISABLE_GQA only move the call off the packed path: the document
+    kernels have a native backward alone (the aten flash backward takes no
+    mask) and map GQA heads themselves, so under auto|native the backward
+    stays native and repeated K/V heads are simply equal head counts."""
+    from ..ops.attention import docs_supported, flash_attention_docs
+    from ..ops.docmask import doc_mask_dense
+    if backend in ("auto", "native"):
+        qc = q.contiguous() if q.stride(-1) != 1 else q
+        if docs_supported(qc, k):
+            return flash_attention_docs(qc, k, v, doc_bounds)
+    mask = doc_mask_dense(doc_bounds)
+    if backend in ("auto", "native") or not q.is_cuda:
+        return F.scaled_dot_product_attention(q, k, v, attn_mask=mask,
+                                              enable_gqa=enable_gqa)
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    mapping = {"flash": SDPBackend.FLASH_ATTENTION,
+               "efficient": SDPBackend.EFFICIENT_ATTENTION,
+               "math": SDPBackend.MATH}
+    with sdpa_kernel([mapping[backend]]):
+        return F.scaled_dot_product_attention(q, k, v, attn_mask=mask,
+                                              enable_gqa=enable_gqa)
+
+
+def _sdpa(q, k, v, enable_gqa=False, is_causal=True, doc_bounds=None):
     """SDPA with a backend override knob (AITJ_SDPA_BACKEND =
     flash|efficient|math|native|library|auto). Default (auto): the
     hand-written CDNA4 kernels (ops/attention.py, fwd AND bwd) whenever the
     shape supports them — they measure 1.38x the aotriton fwd+bwd at the
     flagship shape — with the library SDPA for everything else (decode
-    shapes, small head_dim)."""
+    shapes, small head_dim). doc_bounds (ops/docmask.py) masks attention at
+    document boundaries: see _sdpa_docs."""
     backend = os.environ.get("AITJ_SDPA_BACKEND", "auto")
+    if doc_bounds is not None:
+        assert is_causal, "a document mask is causal inside each document"
+        return _sdpa_docs(q, k, v, doc_bounds, enable_gqa, backend)
     if q.is_cuda and backend in ("auto", "native") and is_causal:
         from ..ops.attention import _supported, flash_attention
         qc = q.contiguous() if q.stride(-1) != 1 else q
@@ -106,7 +141,8 @@ class Attention(nn.Module):
                                   bias=False)
         self.o_proj = nn.Linear(self.q_size, H, bias=False)
 
-    def forward(self, x: torch.Tensor, inv_freq: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, inv_freq: torch.Tensor,
+                doc_bounds: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, S, H = x.shape
         cfg = self.cfg
         qkv = _proj(x, self.qkv_proj)
@@ -115,7 +151,8 @@ class Attention(nn.Module):
             # q/k copies, no output transpose copy, no cat in the backward
             from ..ops.attention import packed_rope_attention
             o = packed_rope_attention(qkv, inv_freq, cfg.num_heads,
-                                      cfg.num_kv_heads)
+                                      cfg.num_kv_heads,
+                                      doc_bounds=doc_bounds)
             return _proj(o, self.o_proj)
         q, k, v = qkv.split([self.q_size, self.kv_size, self.kv_size],
                             dim=-1)
@@ -136,10 +173,11 @@ class Attention(nn.Module):
             groups = cfg.num_heads // cfg.num_kv_heads
             k = k.repeat_interleave(groups, dim=1)
             v = v.repeat_interleave(groups, dim=1)
-            o = _sdpa(q, k, v)
+            o = _sdpa(q, k, v, doc_bounds=doc_bounds)
         else:
             o = _sdpa(q, k, v,
-                      enable_gqa=cfg.num_heads != cfg.num_kv_heads)
+                      enable_gqa=cfg.num_heads != cfg.num_kv_heads,
+                      doc_bounds=doc_bounds)
         o = o.transpose(1, 2).reshape(B, S, cfg.num_heads * cfg.head_dim)
         return _proj(o, self.o_proj)
 
@@ -168,12 +206,14 @@ class Block(nn.Module):
         self.post_attn_norm_weight = nn.Parameter(torch.ones(cfg.hidden_size))
 
     def forward(self, x: torch.Tensor, residual: Optional[torch.Tensor],
-                inv_freq: torch.Tensor):
+                inv_freq: torch.Tensor,
+                doc_bounds: Optional[torch.Tensor] = None):
         """Pre-norm block over a carried residual stream:
-        (x = branch output, residual = running stream)."""
+        (x = branch output, residual = running stream). doc_bounds: the
+        batch's document layout (ops/docmask.py), None = plain causal."""
         normed, residual = fused_rmsnorm(x, self.input_norm_weight, residual,
                                          self.cfg.norm_eps)
-        attn_out = self.attn(normed, inv_freq)
+        attn_out = self.attn(normed, inv_freq, doc_bounds)
         normed, residual = fused_rmsnorm(attn_out, self.post_attn_norm_weight,
                                          residual, self.cfg.norm_eps)
         mlp_out = self.mlp(normed)
@@ -210,8 +250,12 @@ class LlamaModel(nn.Module):
             nn.init.normal_(blk.attn.o_proj.weight, std=std * scale)
             nn.init.normal_(blk.mlp.down_proj.weight, std=std * scale)
 
-    def forward_hidden(self, tokens: torch.Tensor) -> torch.Tensor:
-        """tokens [B, S] -> final normed hidden [B, S, H]."""
+    def forward_hidden(self, tokens: torch.Tensor,
+                       doc_bounds: Optional[torch.Tensor] = None
+                       ) -> torch.Tensor:
+        """tokens [B, S] -> final normed hidden [B, S, H]. doc_bounds
+        (int32 [2,B,S], ops/docmask.py) masks attention at document
+        boundaries in every layer; RoPE positions stay window-absolute."""
         x = self.embed(tokens)
         residual = None
         for blk in self.blocks:
@@ -219,17 +263,19 @@ class LlamaModel(nn.Module):
                 if residual is None:
                     residual = torch.zeros_like(x)
                 x, residual = torch.utils.checkpoint.checkpoint(
-                    blk, x, residual, self.inv_freq, use_reentrant=False)
+                    blk, x, residual, self.inv_freq, doc_bounds,
+                    use_reentrant=False)
             else:
-                x, residual = blk(x, residual, self.inv_freq)
+                x, residual = blk(x, residual, self.inv_freq, doc_bounds)
         normed, _ = fused_rmsnorm(x, self.final_norm_weight, residual,
                                   self.cfg.norm_eps)
         return normed
 
     def forward(self, tokens: torch.Tensor,
-                targets: Optional[torch.Tensor] = None):
+                targets: Optional[torch.Tensor] = None,
+                doc_bounds: Optional[torch.Tensor] = None):
         """Returns loss (scalar, fp32) when targets given, else logits."""
-        hidden = self.forward_hidden(tokens)
+        hidden = self.forward_hidden(tokens, doc_bounds)
         logits = self.lm_head(hidden)
         if targets is None:
             return logits

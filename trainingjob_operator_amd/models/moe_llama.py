@@ -100,7 +100,13 @@ class MoELlamaModel(nn.Module):
                              make_inv_freq(cfg.head_dim, cfg.rope_theta),
                              persistent=False)
 
-    def forward(self, tokens, targets=None):
+    def forward(self, tokens, targets=None, doc_bounds=None):
+        if doc_bounds is not None:
+            raise ValueError(
+                "MoELlamaModel has no document-masked attention (doc_bounds): "
+                "only the dense LlamaModel passes a document layout down; "
+                "running without the mask would silently attend across "
+                "documents")
         x = self.embed(tokens)
         residual = None
         for blk in self.blocks:

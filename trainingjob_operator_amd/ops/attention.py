@@ -83,6 +83,32 @@ has at most one workgroup per CU dk pairs and dv folds (the flagship step
 does), above that both keep the identity. `lib.attn_bwd_pair_decode` is
 the host copy of the ownership function and `lib.attn_bwd_fold_mode` says
 which ownership a launch of a given shape gets.
+
+Document-masked attention (`flash_attention_docs`, `packed_rope_attention(
+..., doc_bounds=)`; layouts in ops/docmask.py): a window that holds several
+documents attends causally inside each one. The layout is one int32 tensor
+bounds [2,B,S] (first and last window index of every token's document); q
+sees kv iff bounds[0,b,q] <= kv <= q, shared by all heads, RoPE positions
+window-absolute (RoPE is relative, so scores inside a document do not
+depend on its offset). `attn_doc_fwd_kernel` and `attn_doc_bwd_dq_kernel`
+are the v7 forward and dq with one int32 load per lane and `kvr < start`
+next to the causal test; the kv walk starts at the tile of the q block's
+first document start, a wave sits out tiles before the smallest start of
+its rows, and every tile that a start cuts is masked.
+`attn_doc_bwd_dv_kernel` / `attn_doc_bwd_dk_kernel` load end per kv row,
+mask q > end and stop the q walk at the tile of the kv block's last document
+end. They use identity strip ownership, unsplit, with no workspace:
+AITJ_ATTN_BWD_FOLD and AITJ_ATTN_BWD_SPLIT do not apply to document
+launches (AITJ_ATTN_SCHED does). One document of S tokens computes the
+causal result bit for bit; block-aligned documents compute what separate
+causal calls compute, bit for bit. All ranges derived from bounds are
+clamped in the kernels (`lib.attn_doc_tiles_decode` is the host copy), so
+any int32 content is memory-safe and only valid layouts are exact;
+`check_doc_bounds` validates one, with a sync, for tests. The causal
+entries, the block ops and the ring are untouched. ops/reference.py holds
+the fp32 twins (`attention_doc_fwd`, `attention_doc_bwd`). Shapes the
+kernels do not cover (CPU, other head sizes, S % 256 != 0) fall back, in
+packed_rope_attention, to SDPA under `doc_mask_dense(bounds)`.
 """
 from __future__ import annotations
 
@@ -93,6 +119,7 @@ from typing import Optional
 import torch
 
 from . import native
+from .docmask import doc_mask_dense
 
 
 def _supported(q: torch.Tensor, k: torch.Tensor) -> bool:
@@ -206,6 +233,111 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# Document-masked causal attention (bounds: ops/docmask.py)
+# ---------------------------------------------------------------------------
+
+def _check_bounds(bounds, B: int, S: int, device) -> None:
+    """Shape, dtype and placement only: the kernels clamp every range they
+    derive from the content, so no value needs a (syncing) look."""
+    assert isinstance(bounds, torch.Tensor), \
+        f"bounds must be an int32 [2,B,S] tensor, got {type(bounds).__name__}"
+    assert bounds.dtype == torch.int32 and tuple(bounds.shape) == (2, B, S) \
+        and bounds.is_contiguous() and bounds.device == device, (
+            f"bounds must be contiguous int32 [2,{B},{S}] on {device}, got "
+            f"{bounds.dtype} {tuple(bounds.shape)} on {bounds.device}")
+
+
+def docs_supported(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Shapes the document kernels cover: GPU bf16 [B,H,S,128] /
+    [B,HKV,S,128], S % 256 == 0, H % HKV == 0, unit last stride."""
+    return block_supported(q, k) and k.shape[2] == q.shape[2]
+
+
+def _run_doc_fwd(q, k, v, bounds, scale):
+    B, H, S, D = q.shape
+    HKV = k.shape[1]
+    _check_bounds(bounds, B, S, q.device)
+    lib = native.load(require=True)
+    out = torch.empty(B, H, S, D, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+    st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(out))
+    rc = lib.attn_doc_fwd_strided(
+        native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        out.data_ptr(), lse.data_ptr(), bounds.data_ptr(), st,
+        B, H, HKV, S, scale)
+    native.check_rc(rc, "attn_doc_fwd_strided",
+                    f"B={B} H={H} HKV={HKV} S={S}")
+    return out, lse
+
+
+def _native_doc_backward(q, k, v, out, lse, gout, bounds, scale):
+    """delta + dq + dv + dk under the document mask (identity strip
+    ownership, unsplit, no workspace)."""
+    B, H, S, D = q.shape
+    HKV = k.shape[1]
+    _check_bounds(bounds, B, S, q.device)
+    lib = native.load(require=True)
+    dout = gout.contiguous()
+    delta = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+    dq = torch.empty(B, H, S, D, dtype=torch.bfloat16, device=q.device)
+    dk = torch.empty(B, HKV, S, D, dtype=torch.bfloat16, device=q.device)
+    dv = torch.empty(B, HKV, S, D, dtype=torch.bfloat16, device=q.device)
+    st = native.stride_array(_tri(q), _tri(k), _tri(v), _tri(out),
+                             _tri(dout), _tri(dq), _tri(dk), _tri(dv))
+    rc = lib.attn_doc_bwd_strided(
+        native.stream_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+        out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+        dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), bounds.data_ptr(), st,
+        B, H, HKV, S, scale)
+    native.check_rc(rc, "attn_doc_bwd_strided",
+                    f"B={B} H={H} HKV={HKV} S={S}")
+    return dq, dk, dv
+
+
+class _NativeDocAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, bounds, scale):
+        out, lse = _run_doc_fwd(q, k, v, bounds, scale)
+        ctx.save_for_backward(q, k, v, out, lse, bounds)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        q, k, v, out, lse, bounds = ctx.saved_tensors
+        return (*_native_doc_backward(q, k, v, out, lse, gout, bounds,
+                                      ctx.scale), None, None)
+
+
+def flash_attention_docs(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                         bounds: torch.Tensor,
+                         scale: Optional[float] = None) -> torch.Tensor:
+    """Document-masked causal flash attention over [B,H,S,128] bf16 with
+    k, v [B,HKV,S,128] (native GQA), S % 256 == 0: q row s sees kv rows
+    bounds[0,b,s] .. s. bounds is a contiguous int32 [2,B,S] on q's device
+    (ops/docmask.py); only its shape is checked here, the kernels are safe
+    for any content and exact for a valid layout. Positions fed to RoPE
+    before this call stay window-absolute: RoPE is relative, so scores
+    inside a document do not depend on its offset."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    assert docs_supported(q, k) and v.shape == k.shape and v.is_cuda \
+        and v.dtype == q.dtype and v.stride(-1) == 1, (
+            f"flash_attention_docs needs GPU bf16 [B,H,S,128] / [B,HKV,S,128] "
+            f"with S%256==0, H%HKV==0, d-contiguous strides; got "
+            f"{tuple(q.shape)} {q.dtype} kv={tuple(k.shape)}")
+    _check_bounds(bounds, q.shape[0], q.shape[2], q.device)
+    return _NativeDocAttention.apply(q, k, v, bounds, scale)
+
+
+def flash_attention_docs_fwd_only(q, k, v, bounds, scale=None):
+    """Forward-only entry returning (out, lse) for tests/benchmarks."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    return _run_doc_fwd(q, k, v, bounds, scale)
+
+
+# ---------------------------------------------------------------------------
 # RoPE + attention straight on the packed QKV projection output
 # ---------------------------------------------------------------------------
 
@@ -255,10 +387,12 @@ class _PackedRopeAttention(torch.autograd.Function):
     """qkv [B,S,(H+2HKV)*128] -> o [B,S,H*128] with no layout copies: one
     RoPE launch over the q|k head range, the v7 forward reading q/k/v and
     writing o through strides; the backward kernels write their head
-    ranges of one dqkv buffer, un-rotated in place by one RoPE launch."""
+    ranges of one dqkv buffer, un-rotated in place by one RoPE launch.
+    With bounds (a document layout, ops/docmask.py) the same buffers and
+    strides go through the document entries instead."""
 
     @staticmethod
-    def forward(ctx, qkv, inv_freq, n_heads, n_kv_heads, scale):
+    def forward(ctx, qkv, inv_freq, n_heads, n_kv_heads, scale, bounds=None):
         B, S, W = qkv.shape
         D = 128
         H, HKV = n_heads, n_kv_heads
@@ -274,20 +408,32 @@ class _PackedRopeAttention(torch.autograd.Function):
         st = native.stride_array(
             _bhsd_strides(R, D, S), _bhsd_strides(R, D, S),
             _bhsd_strides(W, D, S), _bhsd_strides(H * D, D, S))
-        rc = lib.attn_fwd_strided(
-            native.stream_ptr(), rot.data_ptr(),
-            rot.data_ptr() + H * D * esz,
-            qkv.data_ptr() + (H + HKV) * D * esz,
-            o.data_ptr(), lse.data_ptr(), st, B, H, HKV, S, scale)
-        native.check_rc(rc, "attn_fwd_strided", f"B={B} H={H} HKV={HKV} S={S}")
-        ctx.save_for_backward(rot, qkv, o, lse, inv_freq)
+        if bounds is None:
+            rc = lib.attn_fwd_strided(
+                native.stream_ptr(), rot.data_ptr(),
+                rot.data_ptr() + H * D * esz,
+                qkv.data_ptr() + (H + HKV) * D * esz,
+                o.data_ptr(), lse.data_ptr(), st, B, H, HKV, S, scale)
+            native.check_rc(rc, "attn_fwd_strided",
+                            f"B={B} H={H} HKV={HKV} S={S}")
+        else:
+            _check_bounds(bounds, B, S, qkv.device)
+            rc = lib.attn_doc_fwd_strided(
+                native.stream_ptr(), rot.data_ptr(),
+                rot.data_ptr() + H * D * esz,
+                qkv.data_ptr() + (H + HKV) * D * esz,
+                o.data_ptr(), lse.data_ptr(), bounds.data_ptr(), st,
+                B, H, HKV, S, scale)
+            native.check_rc(rc, "attn_doc_fwd_strided",
+                            f"B={B} H={H} HKV={HKV} S={S}")
+        ctx.save_for_backward(rot, qkv, o, lse, inv_freq, bounds)
         ctx.dims = (B, S, H, HKV, D)
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, gout):
-        rot, qkv, o, lse, inv_freq = ctx.saved_tensors
+        rot, qkv, o, lse, inv_freq, bounds = ctx.saved_tensors
         B, S, H, HKV, D = ctx.dims
         W, R = (H + 2 * HKV) * D, (H + HKV) * D
         lib = native.load(require=True)
@@ -299,21 +445,35 @@ class _PackedRopeAttention(torch.autograd.Function):
         rs, ws, os_ = (_bhsd_strides(R, D, S), _bhsd_strides(W, D, S),
                        _bhsd_strides(H * D, D, S))
         st = native.stride_array(rs, rs, ws, os_, os_, ws, ws, ws)
-        ws, ws_ptr, ws_bytes = _bwd_workspace(lib, B, H, HKV, S, True,
-                                              qkv.device)
-        rc = lib.attn_bwd_strided_ws(
-            native.stream_ptr(), rot.data_ptr(),
-            rot.data_ptr() + H * D * esz,
-            qkv.data_ptr() + (H + HKV) * D * esz,
-            o.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-            dqkv.data_ptr(), dqkv.data_ptr() + H * D * esz,
-            dqkv.data_ptr() + (H + HKV) * D * esz,
-            st, B, H, HKV, S, ctx.scale, ws_ptr, ws_bytes)
-        native.check_rc(rc, "attn_bwd_strided_ws",
-                        f"B={B} H={H} HKV={HKV} S={S}")
+        if bounds is None:
+            ws, ws_ptr, ws_bytes = _bwd_workspace(lib, B, H, HKV, S, True,
+                                                  qkv.device)
+            rc = lib.attn_bwd_strided_ws(
+                native.stream_ptr(), rot.data_ptr(),
+                rot.data_ptr() + H * D * esz,
+                qkv.data_ptr() + (H + HKV) * D * esz,
+                o.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                delta.data_ptr(),
+                dqkv.data_ptr(), dqkv.data_ptr() + H * D * esz,
+                dqkv.data_ptr() + (H + HKV) * D * esz,
+                st, B, H, HKV, S, ctx.scale, ws_ptr, ws_bytes)
+            native.check_rc(rc, "attn_bwd_strided_ws",
+                            f"B={B} H={H} HKV={HKV} S={S}")
+        else:
+            rc = lib.attn_doc_bwd_strided(
+                native.stream_ptr(), rot.data_ptr(),
+                rot.data_ptr() + H * D * esz,
+                qkv.data_ptr() + (H + HKV) * D * esz,
+                o.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+                delta.data_ptr(),
+                dqkv.data_ptr(), dqkv.data_ptr() + H * D * esz,
+                dqkv.data_ptr() + (H + HKV) * D * esz,
+                bounds.data_ptr(), st, B, H, HKV, S, ctx.scale)
+            native.check_rc(rc, "attn_doc_bwd_strided",
+                            f"B={B} H={H} HKV={HKV} S={S}")
         _rope_packed(lib, dqkv, dqkv, inv_freq, B * S, H + HKV, W, W, S, D,
                      -1.0)
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None
 
 
 def packed_supported(qkv: torch.Tensor, n_heads: int, n_kv_heads: int) -> bool:
@@ -324,11 +484,14 @@ def packed_supported(qkv: torch.Tensor, n_heads: int, n_kv_heads: int) -> bool:
             and qkv.shape[2] == (n_heads + 2 * n_kv_heads) * 128)
 
 
-def unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale=None):
+def unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale=None,
+                            doc_bounds=None):
     """The copying composition packed_rope_attention replaces (and its
     fallback): split, dense q/k, RoPE each, [B,h,S,D] attention, transpose
     back. Any head_dim; native flash attention where it applies, torch
-    SDPA elsewhere."""
+    SDPA elsewhere. With doc_bounds the attention is flash_attention_docs
+    where that applies and SDPA under doc_mask_dense(doc_bounds) elsewhere;
+    RoPE positions stay window-absolute either way."""
     from .functional import apply_rope
     B, S, W = qkv.shape
     D = W // (n_heads + 2 * n_kv_heads)
@@ -339,7 +502,14 @@ def unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale=None):
     q = apply_rope(q, inv_freq, S).transpose(1, 2)
     k = apply_rope(k, inv_freq, S).transpose(1, 2)
     v = v.transpose(1, 2)
-    if qkv.is_cuda and _supported(q, k):
+    if doc_bounds is not None:
+        if docs_supported(q, k):
+            o = flash_attention_docs(q, k, v, doc_bounds, scale)
+        else:
+            o = torch.nn.functional.scaled_dot_product_attention(
+                q, k, v, attn_mask=doc_mask_dense(doc_bounds), scale=scale,
+                enable_gqa=n_heads != n_kv_heads)
+    elif qkv.is_cuda and _supported(q, k):
         o = flash_attention(q, k, v, scale)
     else:
         o = torch.nn.functional.scaled_dot_product_attention(
@@ -350,17 +520,27 @@ def unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale=None):
 
 def packed_rope_attention(qkv: torch.Tensor, inv_freq: torch.Tensor,
                           n_heads: int, n_kv_heads: int,
-                          scale: Optional[float] = None) -> torch.Tensor:
+                          scale: Optional[float] = None,
+                          doc_bounds: Optional[torch.Tensor] = None
+                          ) -> torch.Tensor:
     """Causal RoPE attention on the fused projection output:
     qkv [B,S,(H+2HKV)*D] -> o [B,S,H*D]. D = 128 bf16 on the GPU with
     S % 256 == 0 runs the copy-free packed kernels; everything else (CPU,
-    other head sizes, other S) runs the unpacked composition."""
+    other head sizes, other S) runs the unpacked composition. doc_bounds
+    (int32 [2,B,S], ops/docmask.py) masks attention at document boundaries:
+    the packed layout then goes through the document entries, still with no
+    copies, and the fallback is SDPA under the dense mask. None is the
+    causal path, unchanged."""
     if packed_supported(qkv, n_heads, n_kv_heads):
         if scale is None:
             scale = 1.0 / math.sqrt(128)
+        if doc_bounds is None:
+            return _PackedRopeAttention.apply(qkv, inv_freq, n_heads,
+                                              n_kv_heads, scale)
         return _PackedRopeAttention.apply(qkv, inv_freq, n_heads, n_kv_heads,
-                                          scale)
-    return unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale)
+                                          scale, doc_bounds)
+    return unpacked_rope_attention(qkv, inv_freq, n_heads, n_kv_heads, scale,
+                                   doc_bounds)
 
 
 def flash_attention_fwd_only(q, k, v, scale=None):

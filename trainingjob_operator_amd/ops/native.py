@@ -153,6 +153,20 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # (batch, heads, kv heads, S, causal, split, kernel 0 dv | 1 dk) -> the
     # ownership a launch gets now: 0 identity, 1 fold, 2 pair
     _sig(lib.attn_bwd_fold_mode, [i, i, i, i, i, i, i], i)
+    # document-masked entries: bounds (device int32 [2,B,S]) before the
+    # stride triples q, k, v, out | q, k, v, out, dout, dq, dk, dv; the
+    # backward runs delta, dq, dv, dk and takes no workspace
+    _sig(lib.attn_doc_fwd_strided, [vp, vp, vp, vp, vp, vp, vp, lp,
+                                    i, i, i, i, f], i)
+    _sig(lib.attn_doc_bwd_strided, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, lp, i, i, i, i, f], i)
+    # one backward kernel alone (part 1 dq | 2 dv | 4 dk, last), for timing:
+    # q, k, v, dout, lse, delta, dq, dk, dv, bounds (null = causal), strides
+    _sig(lib.attn_bwd_part, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, lp,
+                             i, i, i, i, f, i], i)
+    # clamped tile ranges of the document kernels (host callable): (kind 0
+    # fwd/dq | 1 dv/dk, start or end, row block, S) -> first, last tile
+    _sig(lib.attn_doc_tiles_decode, [i, i, i, i, ip, ip], i)
     _sig(lib.mfma_probe32, [vp, vp, vp, vp])
     assert lib.hipops_arch_check() == 950
     _lib = lib

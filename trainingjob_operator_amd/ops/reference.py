@@ -194,6 +194,47 @@ def attention_block_bwd(q, k, v, dout, lse, delta, causal: bool,
     return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
 
 
+def _doc_scores(q, k, bounds, scale: float) -> torch.Tensor:
+    from .docmask import doc_mask_dense
+    s = _block_scores(q, k, False, scale)
+    return s.masked_fill(~doc_mask_dense(bounds), float("-inf"))
+
+
+def attention_doc_fwd(q, k, v, bounds, scale: Optional[float] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Twin of the document-masked forward (ops/docmask.py: q sees kv iff
+    bounds[0,b,q] <= kv <= q): (o in q.dtype, lse fp32 [B,H,S])."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    s = _doc_scores(q, k, bounds, scale)
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    o = torch.matmul(p, _expand_kv(v, q.shape[1]).float())
+    return o.to(q.dtype), lse
+
+
+def attention_doc_bwd(q, k, v, dout, lse, delta, bounds,
+                      scale: Optional[float] = None):
+    """Twin of the document-masked backward: dq, dk, dv from lse and delta,
+    dk/dv at k's head count, all in the input dtypes."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    B, H, S, D = q.shape
+    HKV = k.shape[1]
+    s = _doc_scores(q, k, bounds, scale)
+    p = torch.exp(s - lse.float().unsqueeze(-1))
+    do32 = dout.float()
+    dv = torch.matmul(p.transpose(-1, -2), do32)
+    dp = torch.matmul(do32, _expand_kv(v, H).float().transpose(-1, -2))
+    ds = p * (dp - delta.float().unsqueeze(-1)) * scale
+    dq = torch.matmul(ds, _expand_kv(k, H).float())
+    dk = torch.matmul(ds.transpose(-1, -2), q.float())
+    if HKV != H:
+        dk = dk.reshape(B, HKV, H // HKV, S, D).sum(dim=2)
+        dv = dv.reshape(B, HKV, H // HKV, S, D).sum(dim=2)
+    return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
+
+
 def attn_merge_(o_acc: torch.Tensor, lse_acc: torch.Tensor,
                 o_blk: torch.Tensor, lse_blk: torch.Tensor) -> None:
     """Fold one block (o_blk, lse_blk) into the fp32 running pair in place.

@@ -813,6 +813,10 @@ class CPTrainer:
         from ..optim import FlatAdamW
         from .flat import FlatParamStore
 
+        if getattr(cfg, "doc_mask", False):
+            raise ValueError(
+                "CPTrainer does not support doc_mask: ring attention has no "
+                "document mask and would attend across documents")
         self.cfg = cfg
         mcfg = CONFIGS[cfg.model]
         self.device = torch.device(device or "cpu")

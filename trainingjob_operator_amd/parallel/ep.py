@@ -491,6 +491,10 @@ class EPTrainer:
         from ..parallel.flat import FlatParamStore, classify_spans
         from ..launcher.data import make_batches
 
+        if getattr(cfg, "doc_mask", False):
+            raise ValueError(
+                "EPTrainer does not support doc_mask: the MoE model has no "
+                "document-masked attention and would attend across documents")
         self.cfg = cfg
         mcfg = CONFIGS[cfg.model]
         self.device = torch.device(device or "cpu")

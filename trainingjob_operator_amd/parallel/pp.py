@@ -423,6 +423,10 @@ class PPTrainer:
         from ..optim import FlatAdamW
         from ..launcher.data import make_batches
 
+        if getattr(cfg, "doc_mask", False):
+            raise ValueError(
+                "PPTrainer does not support doc_mask: the pipeline stages "
+                "carry no document layout and would attend across documents")
         self.cfg = cfg
         mcfg = CONFIGS[cfg.model]
         self.device = torch.device(device or "cpu")

@@ -115,8 +115,9 @@ class PSWorker:
         cfg = self.cfg
         loss = None
         for _ in range(cfg.grad_accum):
-            tokens, targets = next(self.data)
-            loss = self.model(tokens, targets)
+            # (tokens, targets) or, with cfg.doc_mask, (tokens, targets,
+            # bounds): the dense model takes the document layout as is
+            loss = self.model(*next(self.data))
             (loss / cfg.grad_accum).backward()
         header = torch.ones(1, dtype=torch.int64)
         for p, (s, e) in enumerate(self.bounds):

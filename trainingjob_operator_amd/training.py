@@ -78,6 +78,25 @@ class TrainConfig:
     warmup_steps: int = 0
     lr_decay_steps: int = 0
     min_lr: float = 0.0
+    # document-masked attention (Llama-3 style): a window that holds
+    # several documents attends causally inside each one. Needs a token
+    # file and the id that ends a document; every batch then carries its
+    # layout (ops/docmask.py) and the dense Trainer hands it to the model.
+    # Dense single-replica-per-GPU training only: the TP/SP/PP/CP/EP
+    # trainers refuse it. Not with use_graphs: the captured step holds two
+    # static tensors per micro-batch and the kernels' tile ranges follow
+    # the layout.
+    doc_mask: bool = False
+    eos_token: int = -1
+
+    def __post_init__(self):
+        if self.doc_mask and not (self.data_path and self.eos_token >= 0):
+            raise ValueError(
+                "doc_mask needs data_path (a token file) and a non-negative "
+                f"eos_token; got data_path={self.data_path!r} "
+                f"eos_token={self.eos_token}")
+        if self.doc_mask and self.use_graphs:
+            raise ValueError("doc_mask cannot be combined with use_graphs")
 
     @property
     def model_config(self) -> LlamaConfig:
@@ -126,6 +145,11 @@ class Trainer:
                 f"{cfg.model!r} is a MoE config: train it with EPTrainer "
                 "(launcher --ep) or PPTrainer (--pp); the dense Trainer "
                 "would silently build a dense model from it")
+        if cfg.doc_mask and cfg.tp_size > 1:
+            raise ValueError(
+                "doc_mask is not supported with tensor or sequence "
+                "parallelism (tp_size > 1): those models have no "
+                "document-masked attention and would attend across documents")
         self.cfg = cfg
         self.ctx = ctx or DistContext()
         if device is None:
@@ -222,10 +246,11 @@ class Trainer:
         cfg = self.cfg
         loss = None
         use_rs = self._zero_rs and not in_graph
-        for micro, (tokens, targets) in enumerate(batches):
+        for micro, batch in enumerate(batches):
+            # (tokens, targets) or, with doc_mask, (tokens, targets, bounds)
             sync = micro == cfg.grad_accum - 1 and not use_rs
             with (nullcontext() if sync else self.ddp.no_sync()):
-                loss = self.model(tokens, targets)
+                loss = self.model(*batch)
                 # scale so accumulated grads average over micro-batches
                 (loss / cfg.grad_accum).backward()
         self.ddp.finish_backward()
