@@ -7,6 +7,7 @@ in the driver-run GPU suite.
 
   python scripts/graphcheck.py            # correctness on llama-smoke
   python scripts/graphcheck.py bench      # llama3-8b b1/b8 decode tok/s
+  python scripts/graphcheck.py --paged    # captured paged engine step
 """
 import os
 import sys
@@ -107,8 +108,54 @@ def session():
           f"{128 / dt:.1f} tok/s, {dt * 1e3 / 128:.2f} ms/token")
 
 
+def paged():
+    """PagedEngine(graph=True): _step_paged captured once at max_slots and
+    replayed while requests of different lengths come and go, against the
+    same engine run eagerly (llama-smoke)."""
+    from trainingjob_operator_amd.models.config import CONFIGS
+    from trainingjob_operator_amd.models.generate import (
+        build_inference_model,
+    )
+    from trainingjob_operator_amd.models.paged import PagedEngine
+    cfg = CONFIGS["llama-smoke"]
+    m = build_inference_model(cfg, torch.device("cuda:0"))
+    g = torch.Generator().manual_seed(9)
+    lengths = [5, 64, 130, 33, 70, 12]
+    news = [24, 9, 30, 17, 40, 8]
+    prompts = [torch.randint(0, cfg.vocab_size, (n,), generator=g)
+               for n in lengths]
+    outs = {}
+    for graph in (False, True):
+        eng = PagedEngine(m, max_slots=4, n_pages=16, max_pages_per_seq=3,
+                          graph=graph)
+        ids = [eng.submit(p, n) for p, n in zip(prompts, news)]
+        done = {}
+        t0 = time.perf_counter()
+        while not eng.idle:
+            for r in eng.step():
+                done[r.id] = r.tokens
+            eng.cache.check_block_table()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert eng.cache.pages_free == eng.cache.n_pages
+        assert eng.graph_mode == graph
+        outs[graph] = [done[i] for i in ids]
+        print(f"paged engine graph={graph}: {eng.steps} steps, "
+              f"{sum(news) / dt:.1f} tok/s (capture included)")
+    same = sum(a == b for x, y in zip(outs[False], outs[True])
+               for a, b in zip(x, y))
+    total = sum(len(x) for x in outs[False])
+    print(f"paged: token agreement graph vs eager: {same / total:.3f} "
+          f"({total} positions)")
+    assert all(len(x) == len(y) for x, y in zip(outs[False], outs[True]))
+    assert same / total > 0.95, outs
+    print("graphcheck paged OK")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "bench":
+    if "--paged" in sys.argv[1:]:
+        paged()
+    elif len(sys.argv) > 1 and sys.argv[1] == "bench":
         bench()
     elif len(sys.argv) > 1 and sys.argv[1] == "session":
         session()

@@ -6,6 +6,7 @@ families an OpenAI-ish token-in/token-out endpoint on an MI355X node:
 
     python -m trainingjob_operator_amd.launcher.serve \
         --model llama3-8b --port 8000 [--ckpt-dir DIR] [--graph]
+        [--paged [--max-slots N] [--pool-pages N]]
 
 The API is deliberately token-level (``prompt_tokens`` → ``tokens``):
 tokenizers are workload assets the cluster may not have offline, and the
@@ -14,6 +15,11 @@ optional hipGraph-captured step (AITJ_DECODE_GRAPH=1 via --graph) — is
 independent of them. Requests are served one at a time from a worker
 thread (decode saturates HBM bandwidth at batch 1; request-level
 batching happens by sending multiple sequences in one request).
+
+With --paged the sequences of all requests share one paged KV cache and
+one decode loop instead (models/paged.PagedEngine): prompts of different
+lengths are accepted, every sequence is its own engine request, and
+concurrent HTTP requests share decode steps rather than queueing.
 
 Endpoints:
     GET  /healthz   liveness + model name
@@ -27,6 +33,7 @@ Endpoints:
 # endpoint type hints at runtime, and the locally-scoped request model
 # would become an unresolvable string under postponed annotations.
 import argparse
+import contextlib
 import threading
 import time
 from typing import List, Optional
@@ -34,9 +41,16 @@ from typing import List, Optional
 import torch
 
 
-def create_app(model, model_name: str = "model"):
+_METRICS = {}
+_PAGED_GAUGES = {}
+
+
+def create_app(model, model_name: str = "model", paged: bool = False,
+               max_slots: int = 8, pool_pages: Optional[int] = None):
     """Build the FastAPI app around an already-constructed model (tests
-    pass a CPU llama-tiny; the CLI builds the named config on cuda:0)."""
+    pass a CPU llama-tiny; the CLI builds the named config on cuda:0).
+    paged=True serves /generate through a PagedEngine of `max_slots`
+    sequences over `pool_pages` 64-row KV pages (default 32 per slot)."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -54,7 +68,16 @@ def create_app(model, model_name: str = "model"):
         # to plain greedy; wins on repetitive text)
         prompt_lookup: int = 0
 
-    app = FastAPI(title="trainingjob-operator-amd serving", version="1.0")
+    on_close = []                    # run when the app shuts down
+
+    @contextlib.asynccontextmanager
+    async def lifespan(_app):
+        yield
+        for fn in on_close:
+            fn()
+
+    app = FastAPI(title="trainingjob-operator-amd serving", version="1.0",
+                  lifespan=lifespan)
     lock = threading.Lock()          # one generation at a time per GPU
     device = next(model.parameters()).device
     sessions = {}                    # batch -> DecodeSession (graph mode)
@@ -62,17 +85,65 @@ def create_app(model, model_name: str = "model"):
         from prometheus_client import (  # operator's metrics use)
             Counter, Histogram, generate_latest,
         )
-        mx = {
-            "requests": Counter("aitj_serve_requests_total",
-                                "Generation requests", ["status"]),
-            "tokens": Counter("aitj_serve_tokens_total",
-                              "Tokens decoded"),
-            "latency": Histogram("aitj_serve_request_seconds",
-                                 "Request wall time",
-                                 buckets=(.05, .2, .5, 1., 2., 5., 15.)),
-        }
+        if not _METRICS:             # a registry takes each name once:
+            _METRICS.update({        # every app of the process shares them
+                "requests": Counter("aitj_serve_requests_total",
+                                    "Generation requests", ["status"]),
+                "tokens": Counter("aitj_serve_tokens_total",
+                                  "Tokens decoded"),
+                "latency": Histogram("aitj_serve_request_seconds",
+                                     "Request wall time",
+                                     buckets=(.05, .2, .5, 1., 2., 5., 15.)),
+            })
+        mx = _METRICS
     except Exception:                # prometheus_client optional
         mx, generate_latest = None, None
+
+    engine = None
+    stop = threading.Event()
+    if paged:
+        import os
+
+        from ..models.paged import PagedEngine
+        model.eval()
+        engine = PagedEngine(
+            model, max_slots=max_slots, n_pages=pool_pages,
+            graph=os.environ.get("AITJ_DECODE_GRAPH") == "1")
+        if mx:
+            # shared like _METRICS; they follow the newest paged app
+            from prometheus_client import Gauge
+            for gname, doc, fn in (
+                    ("aitj_serve_pages_free", "Free KV-cache pages",
+                     lambda: engine.cache.pages_free),
+                    ("aitj_serve_active_slots", "Sequences being decoded",
+                     lambda: engine.n_active)):
+                if gname not in _PAGED_GAUGES:
+                    _PAGED_GAUGES[gname] = Gauge(gname, doc)
+                _PAGED_GAUGES[gname].set_function(fn)
+
+        def _engine_loop():
+            # the ONE thread that steps the engine: handlers enqueue and
+            # wait on their requests' events. A step that raises fails
+            # every pending request (engine._fail_all), so nobody hangs.
+            while not stop.is_set():
+                engine.wait_for_work(stop)
+                if stop.is_set():
+                    break
+                try:
+                    engine.step()
+                except Exception:
+                    pass
+
+        worker = threading.Thread(target=_engine_loop, daemon=True,
+                                  name="paged-engine")
+        worker.start()
+
+        def _stop_engine():
+            stop.set()
+            engine.wake()
+            worker.join(timeout=5)
+
+        on_close.append(_stop_engine)
 
     def _session(batch: int, need_len: int):
         """Reuse a captured-graph session per batch size (the capture is
@@ -103,12 +174,17 @@ def create_app(model, model_name: str = "model"):
     def info():
         import os
         cfg = model.cfg
-        return {
+        body = {
             "model": model_name, "device": str(device),
             "vocab_size": cfg.vocab_size, "num_layers": cfg.num_layers,
             "hidden_size": cfg.hidden_size,
             "graph_decode": os.environ.get("AITJ_DECODE_GRAPH") == "1",
         }
+        if engine is not None:
+            body.update(paged=True, max_slots=engine.max_slots,
+                        pages_total=engine.cache.n_pages,
+                        pages_free=engine.cache.pages_free)
+        return body
 
     @app.get("/metrics")
     def metrics():
@@ -117,6 +193,40 @@ def create_app(model, model_name: str = "model"):
             raise HTTPException(404, "prometheus_client not installed")
         return PlainTextResponse(generate_latest().decode())
 
+    def _gen_paged(req):
+        """Every sequence becomes its own engine request; the engine
+        thread decodes them together with whatever else is in flight."""
+        t0 = time.perf_counter()
+        for p in req.prompt_tokens:
+            if not engine.cache.can_ever_fit(len(p) + req.max_new_tokens):
+                raise HTTPException(
+                    400, f"prompt of {len(p)} tokens + max_new_tokens "
+                         "does not fit the KV page pool")
+        reqs = []
+        try:
+            for p in req.prompt_tokens:
+                reqs.append(engine.submit_request(
+                    p, req.max_new_tokens, req.temperature, req.top_k,
+                    req.eos_token, req.seed))
+        except ValueError as e:
+            raise HTTPException(400, str(e))
+        for r in reqs:
+            r.done.wait()
+        dt = time.perf_counter() - t0
+        if any(r.error is not None for r in reqs):
+            if mx:
+                mx["requests"].labels(status="error").inc()
+            raise HTTPException(500, "decode failed: "
+                                + repr(next(r.error for r in reqs
+                                            if r.error is not None)))
+        n_new = sum(r.n_new for r in reqs)
+        if mx:
+            mx["requests"].labels(status="ok").inc()
+            mx["tokens"].inc(n_new)
+            mx["latency"].observe(dt)
+        return {"tokens": [r.tokens for r in reqs],
+                "decode_tok_s": round(n_new / dt, 1)}
+
     @app.post("/generate")
     def gen(req: GenerateRequest):
         if mx:
@@ -124,7 +234,7 @@ def create_app(model, model_name: str = "model"):
         if not req.prompt_tokens or not all(req.prompt_tokens):
             raise HTTPException(400, "prompt_tokens must be non-empty")
         lens = {len(p) for p in req.prompt_tokens}
-        if len(lens) != 1:
+        if len(lens) != 1 and engine is None:
             raise HTTPException(
                 400, "all prompts in a batch must share a length "
                      "(pad on the client)")
@@ -133,6 +243,10 @@ def create_app(model, model_name: str = "model"):
         vocab = model.cfg.vocab_size
         if any(t < 0 or t >= vocab for p in req.prompt_tokens for t in p):
             raise HTTPException(400, f"token id out of range [0,{vocab})")
+        if engine is not None and not (
+                req.prompt_lookup > 0 and req.temperature <= 0
+                and len(req.prompt_tokens) == 1):
+            return _gen_paged(req)
         prompt = torch.tensor(req.prompt_tokens, dtype=torch.long,
                               device=device)
         with lock:
@@ -189,6 +303,14 @@ def main(argv=None):
                          "init — benchmarking mode)")
     ap.add_argument("--graph", action="store_true",
                     help="hipGraph-captured decode (AITJ_DECODE_GRAPH=1)")
+    ap.add_argument("--paged", action="store_true",
+                    help="paged KV cache + continuous batching: ragged "
+                         "prompts, concurrent requests share decode steps")
+    ap.add_argument("--max-slots", type=int, default=8,
+                    help="sequences decoded together (with --paged)")
+    ap.add_argument("--pool-pages", type=int, default=None,
+                    help="64-row KV pages in the pool (with --paged; "
+                         "default 32 per slot)")
     args = ap.parse_args(argv)
     if args.graph:
         os.environ["AITJ_DECODE_GRAPH"] = "1"
@@ -198,7 +320,8 @@ def main(argv=None):
         from .checkpoint import load_model_only
         step = load_model_only(args.ckpt_dir, model)
         print(f"loaded checkpoint step {step} from {args.ckpt_dir}")
-    app = create_app(model, args.model)
+    app = create_app(model, args.model, paged=args.paged,
+                     max_slots=args.max_slots, pool_pages=args.pool_pages)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 
 

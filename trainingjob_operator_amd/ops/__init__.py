@@ -8,6 +8,7 @@ numerics tests in tests/test_ops_gpu.py.
 from .functional import (
     apply_rope,
     decode_attention,
+    decode_attention_paged,
     decode_linear,
     decode_swiglu,
     fused_cross_entropy,
@@ -16,6 +17,7 @@ from .functional import (
     gather_rows,
     make_inv_freq,
     moe_combine,
+    rope_cache_paged,
     swiglu,
     swiglu_packed,
 )
@@ -24,6 +26,7 @@ from .native import HipOpsUnavailable, available, build_ops, load
 __all__ = [
     "apply_rope",
     "decode_attention",
+    "decode_attention_paged",
     "decode_linear",
     "decode_swiglu",
     "dispatch_rows",
@@ -32,6 +35,7 @@ __all__ = [
     "fused_cross_entropy",
     "fused_rmsnorm",
     "make_inv_freq",
+    "rope_cache_paged",
     "swiglu",
     "available",
     "build_ops",

@@ -268,6 +268,87 @@ def decode_attention(q: torch.Tensor, kc: torch.Tensor,
     return o[:, :, None, :]
 
 
+def decode_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, block_table: torch.Tensor,
+                           pos: torch.Tensor,
+                           scale: float) -> Optional[torch.Tensor]:
+    """decode_attention over a PAGED cache with a position per sequence
+    (hip/ops.hip attn_decode_paged). Pools [n_pages, n_kv, 64, D];
+    block_table [B, max_pages] int32 names the physical page of every
+    logical page of slot b; pos [B] int64 is the row this step's token
+    occupies (rows 0..pos[b] are attended), negative = idle slot, whose
+    output is zeros. One wave per (head, page); waves beyond pos[b] exit
+    before touching memory. Same contract as decode_attention: returns
+    [B, H, 1, D], or None when the shape is unsupported (the caller falls
+    back to reference.decode_attention_paged). Inference-only."""
+    B, H, S, D = q.shape
+    n_pages, n_kv, R = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
+    G = H // n_kv if H % n_kv == 0 else 0
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and D == 128
+            and S == 1 and G >= 1 and R == reference.PAGE_ROWS
+            and k_pool.dtype == torch.bfloat16
+            and k_pool.shape == v_pool.shape
+            and k_pool.is_contiguous() and v_pool.is_contiguous()
+            and block_table.dtype == torch.int32
+            and block_table.dim() == 2 and block_table.shape[0] == B
+            and block_table.is_contiguous()
+            and pos.dtype == torch.int64 and pos.shape == (B,)
+            and pos.is_contiguous()):
+        return None
+    lib = _hip()
+    max_pages = block_table.shape[1]
+    q2 = q.reshape(B, H, D).contiguous()
+    partial = torch.empty(B, n_kv, max_pages, G, 130, dtype=torch.float32,
+                          device=q.device)
+    o = torch.empty(B, H, D, dtype=torch.bfloat16, device=q.device)
+    rc = lib.attn_decode_paged(native.stream_ptr(), _ptr(q2), _ptr(k_pool),
+                               _ptr(v_pool), _ptr(block_table), _ptr(pos),
+                               _ptr(partial), _ptr(o), B, H, n_kv, n_pages,
+                               max_pages, scale)
+    native.check_rc(rc, "attn_decode_paged",
+                    f"H={H} n_kv={n_kv} max_pages={max_pages}")
+    return o[:, :, None, :]
+
+
+def rope_cache_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
+                     v_pool: torch.Tensor, inv_freq: torch.Tensor,
+                     block_table: torch.Tensor, pos: torch.Tensor,
+                     num_heads: int, num_kv_heads: int) -> torch.Tensor:
+    """Fused decode rope + PAGED cache write (hip/ops.hip
+    rope_cache_paged): qkv [B, (nh+2*nkv)*D] packed q | k | v; ropes q
+    into the returned [B, nh, D] buffer, ropes k and copies v into row
+    pos[b] % 64 of page block_table[b][pos[b] // 64] of the pools, in
+    place. An idle slot (pos[b] < 0) writes no k/v and gets a zero q.
+    Off-GPU (or fp32) the torch reference does the same work."""
+    n_pages, _, R, D = k_pool.shape
+    B = qkv.shape[0]
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and k_pool.dtype == torch.bfloat16
+            and inv_freq.dtype == torch.float32
+            and R == reference.PAGE_ROWS):
+        return reference.rope_cache_paged(qkv, k_pool, v_pool, inv_freq,
+                                          block_table, pos, num_heads,
+                                          num_kv_heads)
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous()
+    assert block_table.shape[0] == B and pos.shape == (B,)
+    assert pos.dtype == torch.int64 and pos.is_contiguous()
+    assert k_pool.shape[1] == num_kv_heads
+    assert qkv.numel() == B * (num_heads + 2 * num_kv_heads) * D
+    lib = _hip()
+    qkv = qkv.contiguous()
+    q = torch.empty(B, num_heads, D, dtype=torch.bfloat16,
+                    device=qkv.device)
+    rc = lib.rope_cache_paged(native.stream_ptr(),
+                              _ptr(qkv), _ptr(q), _ptr(k_pool),
+                              _ptr(v_pool), _ptr(inv_freq),
+                              _ptr(block_table), _ptr(pos), B, num_heads,
+                              num_kv_heads, n_pages, block_table.shape[1],
+                              D)
+    native.check_rc(rc, "rope_cache_paged", f"D={D}")
+    return q
+
+
 def decode_swiglu(x: torch.Tensor,
                   gate_up_weight: torch.Tensor) -> Optional[torch.Tensor]:
     """silu(x @ Wg^T) * (x @ Wu^T) over the packed [2F, K] gate|up weight

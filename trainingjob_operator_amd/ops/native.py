@@ -77,6 +77,14 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.attn_decode, [vp, vp, vp, vp, vp, vp, vp,
                            i, i, i, i, i, f], i)
     _sig(lib.rope_cache, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
+    # paged decode: (q, k_pool, v_pool, block_table int32 [B, max_pages],
+    # pos int64 [B], partial, o, B, H, n_kv, n_pages, max_pages, scale)
+    _sig(lib.attn_decode_paged, [vp, vp, vp, vp, vp, vp, vp, vp,
+                                 i, i, i, i, i, f], i)
+    # (qkv, qout, k_pool, v_pool, inv_freq, block_table, pos, B, nh, nkv,
+    # n_pages, max_pages, D)
+    _sig(lib.rope_cache_paged, [vp, vp, vp, vp, vp, vp, vp, vp,
+                                i, i, i, i, i, i], i)
     _sig(lib.swiglu_fwd, [vp, vp, vp, vp, l], i)
     _sig(lib.swiglu_bwd, [vp, vp, vp, vp, vp, vp, l], i)
     _sig(lib.swiglu_packed_fwd, [vp, vp, vp, l, i], i)

@@ -71,6 +71,85 @@ def rope_at(x: torch.Tensor, inv_freq: torch.Tensor, positions: torch.Tensor,
                       x1 * sin + x2 * cos], dim=-1).to(x.dtype)
 
 
+PAGE_ROWS = 64      # rows per KV-cache page (== the decode kernel's chunk)
+
+
+def _paged_gather(pool: torch.Tensor, block_table: torch.Tensor
+                  ) -> torch.Tensor:
+    """pool [n_pages, n_kv, 64, D] through block_table [B, max_pages] ->
+    the logical caches [B, n_kv, max_pages*64, D]. Table entries are
+    clamped into the pool like the kernels clamp them."""
+    B, max_pages = block_table.shape
+    n_pages, n_kv, R, D = pool.shape
+    tbl = block_table.long().clamp(0, n_pages - 1)
+    return pool[tbl].permute(0, 2, 1, 3, 4).reshape(
+        B, n_kv, max_pages * R, D)
+
+
+def decode_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, block_table: torch.Tensor,
+                           pos: torch.Tensor, scale: float) -> torch.Tensor:
+    """Twin of attn_decode_paged: q [B,H,1,D] attends rows 0..pos[b] of
+    slot b's pages; fp32 math, any head_dim, result in q.dtype. A slot
+    with pos[b] < 0 is idle and comes out as zeros. Rows beyond pos[b]
+    are never used, whatever they hold."""
+    B, H, _, D = q.shape
+    n_kv = k_pool.shape[1]
+    G = H // n_kv
+    k = _paged_gather(k_pool, block_table).float()
+    v = _paged_gather(v_pool, block_table).float()
+    L = k.shape[2]
+    valid = (torch.arange(L, device=q.device)[None, :]
+             <= pos.to(q.device)[:, None])                  # [B, L]
+    vm = valid[:, None, :, None]
+    k = torch.where(vm, k, torch.zeros_like(k))
+    v = torch.where(vm, v, torch.zeros_like(v))
+    s = torch.einsum("bkgd,bksd->bkgs", q.reshape(B, n_kv, G, D).float(),
+                     k) * scale
+    s = s.masked_fill(~valid[:, None, None, :], float("-inf"))
+    active = (pos.to(q.device) >= 0)[:, None, None, None]
+    s = torch.where(active, s, torch.zeros_like(s))         # idle: no nan
+    p = torch.softmax(s, dim=-1)
+    o = torch.einsum("bkgs,bksd->bkgd", p, v)
+    o = torch.where(active, o, torch.zeros_like(o))
+    return o.reshape(B, H, 1, D).to(q.dtype)
+
+
+def rope_cache_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
+                     v_pool: torch.Tensor, inv_freq: torch.Tensor,
+                     block_table: torch.Tensor, pos: torch.Tensor,
+                     num_heads: int, num_kv_heads: int) -> torch.Tensor:
+    """Twin of rope_cache_paged: qkv [B, (nh+2*nkv)*D] packed q | k | v.
+    Ropes q and k (neox, fp32) at pos[b], writes k and v into row pos%64
+    of page block_table[b][pos//64] IN PLACE and returns q [B, nh, D].
+    An idle slot (pos[b] < 0) writes nothing and gets a zero q."""
+    n_pages, _, R, D = k_pool.shape
+    B = qkv.shape[0]
+    half = D // 2
+    x = qkv.reshape(B, num_heads + 2 * num_kv_heads, D)
+    q, k, v = x.split([num_heads, num_kv_heads, num_kv_heads], dim=1)
+    pos = pos.to(qkv.device)
+    active = pos >= 0
+    p = pos.clamp(0, block_table.shape[1] * R - 1)
+    ang = p.float()[:, None] * inv_freq[None, :].float()   # [B, half]
+    cos, sin = torch.cos(ang)[:, None, :], torch.sin(ang)[:, None, :]
+
+    def rot(t):
+        tf = t.float()
+        t1, t2 = tf[..., :half], tf[..., half:]
+        return torch.cat([t1 * cos - t2 * sin,
+                          t1 * sin + t2 * cos], dim=-1).to(t.dtype)
+
+    qr, kr = rot(q), rot(k)
+    qr = torch.where(active[:, None, None], qr, torch.zeros_like(qr))
+    page = block_table.long().gather(1, (p // R)[:, None]).squeeze(1)
+    page = page.clamp(0, n_pages - 1)
+    row = p % R
+    k_pool[page[active], :, row[active]] = kr[active].to(k_pool.dtype)
+    v_pool[page[active], :, row[active]] = v[active].to(v_pool.dtype)
+    return qr.contiguous()
+
+
 def swiglu_fwd(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     gf = g.float()
     return (gf * torch.sigmoid(gf) * u.float()).to(g.dtype)
