@@ -2,15 +2,18 @@
 """Per-kernel ISA summary of the attention source, and its comparison.
 
   attnisa.py dump OUT.json [--src attention.hip]
-  attnisa.py diff A.json B.json
+  attnisa.py diff A.json B.json [--pair A_SUBSTRING=B_SUBSTRING ...]
 
 dump compiles the attention source to gfx950 assembly with the flags of
 native.build_ops (device side only, no GPU needed) and writes, per kernel
 symbol: VGPR and SGPR counts, scratch and LDS bytes, the instruction count,
 a hash of the instruction stream with comments and local labels stripped,
 and the histogram of mnemonics. diff prints `identical` per kernel, or the
-metadata and histogram entries that changed. To compare a branch with its
-parent, dump each from its own checkout (`git worktree add DIR REV`, then
+metadata and histogram entries that changed. Kernels pair by mangled symbol;
+one that was renamed, or whose template or argument list changed, is named
+with --pair, e.g. --pair attn_bwd_dq_kernelILb1E=attn_bwd_dq_kernelILi1E.
+To compare a branch with its parent, dump each from its own checkout (`git
+worktree add DIR REV`, then
 `--src DIR/trainingjob_operator_amd/ops/hip/attention.hip`).
 
 The compiler version decides the output, so this is a tool, not a test.
@@ -116,24 +119,44 @@ def dump(args) -> int:
     return 0
 
 
+def only_match(kernels: dict, sub: str, side: str) -> str:
+    """The one kernel symbol of a dump that contains sub."""
+    names = [n for n in kernels if sub in n]
+    if len(names) != 1:
+        raise SystemExit(f"--pair: {sub!r} matches {len(names)} kernels of "
+                         f"{side}: {' '.join(sorted(names)) or 'none'}")
+    return names[0]
+
+
 def diff(args) -> int:
     with open(args.a) as f:
         a = json.load(f)
     with open(args.b) as f:
         b = json.load(f)
+    renamed = {}                     # name in A -> name in B
+    for spec in args.pair:
+        sub_a, _, sub_b = spec.partition("=")
+        na, nb = only_match(a, sub_a, "A"), only_match(b, sub_b, "B")
+        if na in b or nb in a:
+            raise SystemExit(f"--pair {spec}: {na if na in b else nb} "
+                             "is in both dumps already")
+        renamed[na] = nb
+    total = len(set(a) | set(b)) - len(renamed)
     changed = 0
-    for name in sorted(set(a) | set(b)):
-        if name not in a or name not in b:
+    for name in sorted((set(a) | set(b)) - set(renamed.values())):
+        other = renamed.get(name, name)
+        if name not in a or other not in b:
             print(f"{name}: only in {'A' if name in a else 'B'}")
             changed += 1
             continue
-        ka, kb = a[name], b[name]
+        ka, kb = a[name], b[other]
+        label = name if other == name else f"{name} -> {other}"
         if ka["stream_sha256"] == kb["stream_sha256"] and all(
                 ka[k] == kb[k] for k in META_KEYS):
-            print(f"{name}: identical")
+            print(f"{label}: identical")
             continue
         changed += 1
-        print(f"{name}: DIFFERENT")
+        print(f"{label}: DIFFERENT")
         for k in (*META_KEYS, "instructions"):
             mark = "" if ka[k] == kb[k] else "   <--"
             print(f"    {k:14s} {ka[k]:6d} -> {kb[k]:6d}{mark}")
@@ -141,7 +164,7 @@ def diff(args) -> int:
         for mn in sorted(set(ha) | set(hb)):
             if ha.get(mn, 0) != hb.get(mn, 0):
                 print(f"    {mn:30s} {ha.get(mn, 0):5d} -> {hb.get(mn, 0):5d}")
-    print(f"{len(set(a) | set(b))} kernels, {changed} differ")
+    print(f"{total} kernels, {changed} differ")
     return 0
 
 
@@ -155,6 +178,11 @@ def main() -> int:
     c = sub.add_parser("diff", help="compare two dumps kernel by kernel")
     c.add_argument("a")
     c.add_argument("b")
+    c.add_argument("--pair", action="append", default=[],
+                   metavar="A_SUBSTRING=B_SUBSTRING",
+                   help="compare the one kernel of A whose symbol contains "
+                        "A_SUBSTRING with the one of B that contains "
+                        "B_SUBSTRING (a renamed kernel); repeatable")
     c.set_defaults(fn=diff)
     args = ap.parse_args()
     return args.fn(args)

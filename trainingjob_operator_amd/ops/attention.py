@@ -90,13 +90,13 @@ documents attends causally inside each one. The layout is one int32 tensor
 bounds [2,B,S] (first and last window index of every token's document); q
 sees kv iff bounds[0,b,q] <= kv <= q, shared by all heads, RoPE positions
 window-absolute (RoPE is relative, so scores inside a document do not
-depend on its offset). `attn_doc_fwd_kernel` and `attn_doc_bwd_dq_kernel`
-are the v7 forward and dq with one int32 load per lane and `kvr < start`
-next to the causal test; the kv walk starts at the tile of the q block's
+depend on its offset). The document mode of `attn_fwd_v7_kernel` and
+`attn_bwd_dq_kernel` is the v7 forward and dq with one int32 load per lane
+and `kvr < start` next to the causal test; the kv walk starts at the tile of the q block's
 first document start, a wave sits out tiles before the smallest start of
 its rows, and every tile that a start cuts is masked.
-`attn_doc_bwd_dv_kernel` / `attn_doc_bwd_dk_kernel` load end per kv row,
-mask q > end and stop the q walk at the tile of the kv block's last document
+That of `attn_bwd_dv_kernel` / `attn_bwd_dk_kernel` loads end per kv row,
+masks q > end and stops the q walk at the tile of the kv block's last document
 end. They use identity strip ownership, unsplit, with no workspace:
 AITJ_ATTN_BWD_FOLD and AITJ_ATTN_BWD_SPLIT do not apply to document
 launches (AITJ_ATTN_SCHED does). One document of S tokens computes the

@@ -927,16 +927,107 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_v6_kernel(
 //     itself needs no barrier: every wave stages by glds exactly the
 //     rows it transposes, so its own counted vmcnt covers them.
 //
-// CAUSAL (also on the dq/dv/dk kernels): true is the causal kernel, tiles
-// up to the diagonal, mask on the diagonal band. false compiles the bound,
-// the tile skip and the mask out: every q block visits all S_kv/64 kv tiles,
-// for the blocks of ring attention that lie wholly below the diagonal. Those
-// may be rectangular: the non-causal kernels take the q length S and the k/v
-// length S_kv apart, the causal ones never read S_kv (S_q == S_kv == S).
-// Pipeline, ring depth, waits and barriers are shared.
+// MASK (also on the dq/dv/dk kernels): ATTN_MASK_CAUSAL is the causal
+// kernel, tiles up to the diagonal, mask on the diagonal band.
+// ATTN_MASK_NONE compiles the bound, the tile skip and the mask out: every q
+// block visits all S_kv/64 kv tiles, for the blocks of ring attention that
+// lie wholly below the diagonal. Those may be rectangular: the non-causal
+// kernels take the q length S and the k/v length S_kv apart, the others never
+// read S_kv (S_q == S_kv == S). ATTN_MASK_DOC is the causal kernel under a
+// per-token document mask (below). Pipeline, ring depth, waits and barriers
+// are shared.
 // ===========================================================================
 
-template <bool CAUSAL>
+#define ATTN_MASK_NONE 0
+#define ATTN_MASK_CAUSAL 1
+#define ATTN_MASK_DOC 2
+
+// ===========================================================================
+// Document-masked causal attention: the ATTN_MASK_DOC instantiations of the
+// v7 forward and the dq/dv/dk kernels. bounds, the last kernel argument
+// (nullptr and never read in the other two modes), is int32 [2, B, S]:
+// bounds[0,b,s] the window index of the first token of s's document (start),
+// bounds[1,b,s] that of its last (end). q sees kv iff start[q] <= kv <= q,
+// which for valid bounds (contiguous intervals, start and end constant on
+// each) equals kv <= q <= end[kv]. The mask is shared by all heads.
+//
+// The text is the causal kernel's; the document lines sit under
+// `if constexpr` and compile-time ternaries on MASK, so the other
+// instantiations keep their instruction streams
+// (profiles/r12_doc_merge.md). What the mode adds:
+//   * fwd/dq: the lane owning q row qrow loads start once and masks
+//     kvr < start next to kvr > qrow. The kv walk begins at the workgroup-
+//     uniform tile attn_doc_tiles_q(start[b, qb*256], qb).first (ring sources,
+//     slots and have2 count from there; the walk has at least 4 tiles, so the
+//     prologue issues two unconditionally); a wave also sits out tiles wholly
+//     before the smallest start of its 32 rows, and masks every tile that
+//     some row's start cuts, not the diagonal band alone.
+//   * dv/dk: the lane owning kv row kvrow loads end once and masks q > end
+//     next to q < kvrow. The q walk stops at the workgroup-uniform tile
+//     attn_doc_tiles_kv(end[b, last row of the block], kvb, S).last. Strip
+//     ownership is the identity (256 neighbouring kv rows per workgroup) as a
+//     compile-time fact, whatever `fold` says; the mode is instantiated
+//     unsplit only, without workspace: q ranges differ per document, so
+//     neither the fold nor the pair balances them (ROADMAP).
+//
+// Any int32 content is safe: a lane's start is clamped to [0, qrow], its end
+// to [kvrow, S-1], and both tile ranges are clamped below, so every address
+// derived from bounds stays inside the operands. Invalid bounds (not a
+// partition) give wrong numbers, never an out-of-range access.
+//
+// Forward and fully masked tiles. A row can meet tiles in which all its
+// entries are masked before its first real score: row 400 of a block whose
+// row 256 belongs to an earlier document, in a strip that also holds rows of
+// that document. Its masked scores are -1e30, so the first such tile sets
+// m_run = -1e30 (alpha 0 from -inf) and P = exp2(-1e30 - -1e30) = 1 on the
+// masked entries: l_run and oacc collect finite garbage. Further masked
+// tiles keep m_run (pm - m_run = 0). The first tile with a real score x has
+// x - m_run > 8, so the wave rescales, and alpha = exp2(-1e30 - x) is exactly
+// 0: garbage * 0 = 0, and from there masked entries give exp2(-1e30 - m) = 0
+// as in the causal kernel. That tile always comes because start <= qrow by
+// the clamp: every row sees its own diagonal entry. The rescale decision is
+// wave-wide (__all), so rows of two documents in one 32-row strip influence
+// each other's rounding (not their masks); the backward has no such coupling.
+// ===========================================================================
+
+struct AttnTiles { int first, last; };       // inclusive 64-row tile range
+
+__host__ __device__ __forceinline__ int attn_clampi(int x, int lo, int hi) {
+  return x < lo ? lo : (x > hi ? hi : x);
+}
+// kv tiles q block qb (256 rows) walks when its first row's document starts
+// at `start`: from that tile, at most the block's own first, to the diagonal
+__host__ __device__ __forceinline__ AttnTiles attn_doc_tiles_q(int start,
+                                                               int qb) {
+  AttnTiles t;
+  t.first = attn_clampi(start / 64, 0, qb * 4);
+  t.last = qb * 4 + 3;
+  return t;
+}
+// q tiles kv block kvb walks when its last row's document ends at `end`
+__host__ __device__ __forceinline__ AttnTiles attn_doc_tiles_kv(int end,
+                                                                int kvb,
+                                                                int S) {
+  AttnTiles t;
+  t.first = kvb * 4;
+  t.last = attn_clampi(end / 64 + 1, kvb * 4 + 1, S / 64) - 1;
+  return t;
+}
+
+// smallest and largest of a per-row value over the wave's 32 rows (lanes
+// low and low + 32 hold the same row), as wave-uniform scalars
+__device__ __forceinline__ void attn_wave_minmax(int x, int& lo, int& hi_) {
+  int mn = x, mx = x;
+#pragma unroll
+  for (int off = 1; off < 32; off <<= 1) {
+    mn = min(mn, __shfl_xor(mn, off, 64));
+    mx = max(mx, __shfl_xor(mx, off, 64));
+  }
+  lo = __builtin_amdgcn_readfirstlane(mn);
+  hi_ = __builtin_amdgcn_readfirstlane(mx);
+}
+
+template <int MASK>
 __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, u16* __restrict__ out,
@@ -946,9 +1037,11 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     long v_sb, long v_sh, long v_ss,
     long o_sb, long o_sh, long o_ss,
     int n_heads, int gqa_group, int S, float scale2, int batch, int sched,
-    int S_kv) {
+    int S_kv, const int* __restrict__ bounds) {
   // S is the q length: row blocks, qb, the lse row base. S_kv, the k/v
   // length of a rectangular block, is read by the non-causal kernel alone.
+  constexpr bool CAUSAL = MASK != ATTN_MASK_NONE;   // documents are causal too
+  constexpr bool DOC = MASK == ATTN_MASK_DOC;
   constexpr int NT = 512;
   const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
                                          sched);
@@ -969,6 +1062,16 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   const int q0w = qb * 256 + wid * 32;
   const int qrow = q0w + low;
 
+  // documents: this row's start, its extremes over the wave's rows, and the
+  // first tile of the workgroup's walk; all 0 in the other modes
+  int start = 0, smin = 0, smax = 0, t_begin = 0;
+  if constexpr (DOC) {
+    const int* startp = bounds + (long)b * S;
+    start = attn_clampi(startp[qrow], 0, qrow);
+    attn_wave_minmax(start, smin, smax);
+    t_begin = attn_doc_tiles_q(startp[qb * 256], qb).first;
+  }
+
   AttnFrag qf[8];
   attn_load_row(qf, q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss,
                 hi);
@@ -977,34 +1080,41 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   attn_zero(oacc);
   float m_run = -INFINITY, l_run = 0.f;
 
-  // causal: tiles up to the diagonal; non-causal: every kv tile
-  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
+  // causal: tiles up to the diagonal (documents: from t_begin, at least 4);
+  // non-causal: every kv tile
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 - t_begin : S_kv / V6_BN;
 
   // glds source pointers (swizzle-inverted, advanced per issue)
-  AttnRingSrc src = attn_ring_src(k + (long)b * k_sb + (long)hkv * k_sh, k_ss,
-                                  v + (long)b * v_sb + (long)hkv * v_sh, v_ss,
-                                  tid);
+  AttnRingSrc src = attn_ring_src(
+      k + (long)b * k_sb + (long)hkv * k_sh + (long)t_begin * V6_BN * k_ss,
+      k_ss,
+      v + (long)b * v_sb + (long)hkv * v_sh + (long)t_begin * V6_BN * v_ss,
+      v_ss, tid);
 
   // prologue: issue tiles 0 and 1; build Vt[0] once tile 0 lands (LDS->LDS
   // transpose of the landed V row image)
   attn_ring_issue(lds, 0, src);
-  if (n_tiles > 1) attn_ring_issue(lds, 1, src);
-  if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
+  if (DOC || n_tiles > 1) attn_ring_issue(lds, 1, src);
+  if (DOC || n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
   v7_barrier();
   attn_transpose(attn_ring_v(lds, 0), attn_ring_t(lds, 0), tid);
   // tile 0's PV reads every wave's share of Vt[0] before the first in-loop
   // barrier (that one sits at the END of tile 0), so publish it here
   v7_barrier();
 
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kv0 = t * V6_BN;
+  for (int t = 0; t < n_tiles; ++t) {          // t counts from t_begin
+    const int kv0 = (t_begin + t) * V6_BN;
     const bool have2 = (t + 2) < n_tiles;
     if (have2) attn_ring_issue(lds, (t + 2) % V7_RING, src);
 
     char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
     char* vtb = attn_ring_t(lds, t & 1);
-    const bool active = !CAUSAL || kv0 <= q0w + 31;
-    const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
+    // documents: also sit out tiles wholly before the wave's smallest start,
+    // and mask every tile that some row's start cuts
+    const bool active =
+        !CAUSAL || (kv0 <= q0w + 31 && (!DOC || kv0 + V6_BN > smin));
+    const bool need_mask =
+        CAUSAL && (kv0 + V6_BN > q0w || (DOC && kv0 < smax));
 
     f32x16 s0, s1;
     AttnFrag pa[4];
@@ -1026,10 +1136,10 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
         for (int r = 0; r < 16; ++r) {
           const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
           float x0 = s0[r] * scale2;
-          if (kvr > qrow) x0 = -1e30f;
+          if (kvr > qrow || (DOC && kvr < start)) x0 = -1e30f;
           s0[r] = x0;
           float x1 = s1[r] * scale2;
-          if (kvr + 32 > qrow) x1 = -1e30f;
+          if (kvr + 32 > qrow || (DOC && kvr + 32 < start)) x1 = -1e30f;
           s1[r] = x1;
           pm = fmaxf(pm, fmaxf(x0, x1));
         }
@@ -1043,6 +1153,9 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
       }
       pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
 
+      // documents (see the header): a row whose tiles so far were all masked
+      // sits at m_run = -1e30 and is rescaled by exactly 0 here at its first
+      // real one
       if (!__all(pm - m_run <= 8.0f)) {
         const float mn = fmaxf(m_run, pm);
         const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
@@ -1178,7 +1291,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(
 #define BQ_V_U16 (V6_BN * ATTN_D)                      // V row image
 #define BQ_BUF_U16 (BQ_K_U16 + BQ_KT_U16 + BQ_V_U16)
 
-template <bool CAUSAL>
+template <int MASK>
 __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, const u16* __restrict__ dout,
@@ -1190,11 +1303,14 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     long do_sb, long do_sh, long do_ss,
     long dq_sb, long dq_sh, long dq_ss,
     int n_heads, int gqa_group, int S, float scale, int batch, int sched,
-    int S_kv) {
+    int S_kv, const int* __restrict__ bounds) {
   // S: q length (row blocks, lse/delta row base); S_kv: k/v length, read by
-  // the non-causal kernel alone (see attn_fwd_v7_kernel).
+  // the non-causal kernel alone; MASK, bounds and the document lines as in
+  // attn_fwd_v7_kernel.
   // v7-style staging: K rows + V rows by glds into 3-slot rings, K^T
   // built LDS->LDS at tile end, ONE raw barrier per tile, counted vmcnt.
+  constexpr bool CAUSAL = MASK != ATTN_MASK_NONE;
+  constexpr bool DOC = MASK == ATTN_MASK_DOC;
   constexpr int NT = 512;
   const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
                                          sched);
@@ -1215,6 +1331,14 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const int q0w = qb * 256 + wid * 32;
   const int qrow = q0w + low;
 
+  int start = 0, smin = 0, smax = 0, t_begin = 0;
+  if constexpr (DOC) {
+    const int* startp = bounds + (long)b * S;
+    start = attn_clampi(startp[qrow], 0, qrow);
+    attn_wave_minmax(start, smin, smax);
+    t_begin = attn_doc_tiles_q(startp[qb * 256], qb).first;
+  }
+
   AttnFrag qf[8], dof[8];
   attn_load_row(qf, q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss,
                 hi);
@@ -1227,30 +1351,35 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   f32x16 dqacc[4];
   attn_zero(dqacc);
 
-  // causal: tiles up to the diagonal; non-causal: every kv tile
-  const int n_tiles = CAUSAL ? (qb + 1) * 4 : S_kv / V6_BN;
+  // causal: tiles up to the diagonal (documents: from t_begin, at least 4);
+  // non-causal: every kv tile
+  const int n_tiles = CAUSAL ? (qb + 1) * 4 - t_begin : S_kv / V6_BN;
 
-  AttnRingSrc src = attn_ring_src(k + (long)b * k_sb + (long)hkv * k_sh, k_ss,
-                                  v + (long)b * v_sb + (long)hkv * v_sh, v_ss,
-                                  tid);
+  AttnRingSrc src = attn_ring_src(
+      k + (long)b * k_sb + (long)hkv * k_sh + (long)t_begin * V6_BN * k_ss,
+      k_ss,
+      v + (long)b * v_sb + (long)hkv * v_sh + (long)t_begin * V6_BN * v_ss,
+      v_ss, tid);
 
   attn_ring_issue(lds, 0, src);
-  if (n_tiles > 1) attn_ring_issue(lds, 1, src);
-  if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
+  if (DOC || n_tiles > 1) attn_ring_issue(lds, 1, src);
+  if (DOC || n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
   v7_barrier();
   attn_transpose(attn_ring_k(lds, 0), attn_ring_t(lds, 0), tid);
   v7_barrier();   // tile 0 reads every wave's share of KT[0]
 
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kv0 = t * V6_BN;
+  for (int t = 0; t < n_tiles; ++t) {          // t counts from t_begin
+    const int kv0 = (t_begin + t) * V6_BN;
     const bool have2 = (t + 2) < n_tiles;
     if (have2) attn_ring_issue(lds, (t + 2) % V7_RING, src);
 
     char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
     char* vb = reinterpret_cast<char*>(attn_ring_v(lds, t % V7_RING));
     char* ktb = attn_ring_t(lds, t & 1);
-    const bool active = !CAUSAL || kv0 <= q0w + 31;
-    const bool need_mask = CAUSAL && kv0 + V6_BN > q0w;
+    const bool active =
+        !CAUSAL || (kv0 <= q0w + 31 && (!DOC || kv0 + V6_BN > smin));
+    const bool need_mask =
+        CAUSAL && (kv0 + V6_BN > q0w || (DOC && kv0 < smax));
 
     AttnFrag pds[4];
     if (active) {
@@ -1275,7 +1404,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
           float x = sx[r] * scale2 - lse2;
           if (need_mask) {
             const int kvr = kv0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (kvr > qrow) x = -1e30f;
+            if (kvr > qrow || (DOC && kvr < start)) x = -1e30f;
           }
           const float p = exp2_raw(x);
           sx[r] = p * (dp[r] - dlt) * scale;
@@ -1321,7 +1450,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 #define BV_DOT_U16 (ATTN_D * (VT_PITCH_B / 2) + 128)
 #define BV_LSE_U16 128                      // 64 f32
 #define BV_BUF_U16 (BV_Q_U16 + BV_DOT_U16 + BV_LSE_U16)
-template <bool CAUSAL, bool SPLIT>
+template <int MASK, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ dout, const float* __restrict__ lse,
@@ -1331,7 +1460,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     long do_sb, long do_sh, long do_ss,
     long dv_sb, long dv_sh, long dv_ss,
     int n_heads, int n_kv_heads, int S, float scale,
-    float* __restrict__ ws, int batch, int sched, int fold, int S_kv_nc) {
+    float* __restrict__ ws, int batch, int sched, int fold, int S_kv_nc,
+    const int* __restrict__ bounds) {
+  // MASK and bounds as in attn_fwd_v7_kernel; documents are unsplit, with
+  // identity strips whatever `fold` holds.
+  constexpr bool CAUSAL = MASK != ATTN_MASK_NONE;
+  constexpr bool DOC = MASK == ATTN_MASK_DOC;
+  static_assert(!(DOC && SPLIT), "the document mode is unsplit only");
   // S is the q length (q tiles, lse/delta row base). The kv length sets the
   // row blocks, the strips and the workspace rows; it is S on the causal
   // path, where the extra argument is never read.
@@ -1363,10 +1498,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 
   // the non-causal walk is equal work already: identity whatever the flag
   const AttnStrips strips = attn_bwd_strips(
-      CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
+      MASK == ATTN_MASK_CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
       __builtin_amdgcn_readfirstlane(wid), S_kv / 256);
   const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;              // this lane's kv row
+
+  // documents: this kv row's end, its extremes over the wave's rows, and the
+  // last q tile of the workgroup's walk (one past it, as qtn)
+  int end = 0, emin = 0, emax = 0, qtn = S / 64;
+  if constexpr (DOC) {
+    const int* endp = bounds + ((long)batch + b) * S;
+    end = attn_clampi(endp[kvrow], kvrow, S - 1);
+    attn_wave_minmax(end, emin, emax);
+    qtn = attn_doc_tiles_kv(endp[kvb * 256 + 255], kvb, S).last + 1;
+  }
 
   // K row in registers (persistent across the whole WG lifetime)
   const u16* kptr = k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
@@ -1379,7 +1524,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
   attn_zero(dvacc);
 
   const int qt0 = CAUSAL ? strips.qt0 : 0;   // first q tile that sees us
-  const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 dtst[2];
 
@@ -1454,8 +1598,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
       char* dob = qb_ + DOTOFF;
       const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
       // this wave's kv rows need q >= kv0w; skip tiles fully in the past
-      const bool active = !CAUSAL || qt * 64 + 63 >= kv0w;
-      const bool need_mask = CAUSAL && qt * 64 < kv0w + 32;
+      // (documents: and those past the largest end of its rows)
+      const bool active =
+          !CAUSAL || (qt * 64 + 63 >= kv0w && (!DOC || qt * 64 <= emax));
+      const bool need_mask =
+          CAUSAL && (qt * 64 < kv0w + 32 || (DOC && qt * 64 + 63 > emin));
 
       AttnFrag pf[4];
       if (active) {
@@ -1471,12 +1618,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
             s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kc].v, s,
                                                         0, 0, 0);
           }
-          // P = 2^(s*scale2 - lse2[q]); mask q < kv
+          // P = 2^(s*scale2 - lse2[q]); mask q < kv (documents: and q > end)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;   // q within sub
             float x = s[r] * scale2 - lse2t[sub * 32 + qr];
-            if (need_mask && qt * 64 + sub * 32 + qr < kvrow) x = -1e30f;
+            const int qa = qt * 64 + sub * 32 + qr;
+            if (need_mask && (qa < kvrow || (DOC && qa > end))) x = -1e30f;
             s[r] = exp2_raw(x);
           }
           // repack P (C[q][kv]) -> B-fragments [k=q chunk][n=kv]
@@ -1539,7 +1687,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #define BK_LSE_U16 128
 #define BK_DLT_U16 128
 #define BK_BUF_U16 (BK_Q_U16 + BK_DO_U16 + BK_QT_U16 + BK_LSE_U16 + BK_DLT_U16)
-template <bool CAUSAL, bool SPLIT>
+template <int MASK, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
     const u16* __restrict__ v, const u16* __restrict__ dout,
@@ -1551,7 +1699,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     long do_sb, long do_sh, long do_ss,
     long dk_sb, long dk_sh, long dk_ss,
     int n_heads, int n_kv_heads, int S, float scale,
-    float* __restrict__ ws, int batch, int sched, int fold, int S_kv_nc) {
+    float* __restrict__ ws, int batch, int sched, int fold, int S_kv_nc,
+    const int* __restrict__ bounds) {
+  constexpr bool CAUSAL = MASK != ATTN_MASK_NONE;            // see dv
+  constexpr bool DOC = MASK == ATTN_MASK_DOC;
+  static_assert(!(DOC && SPLIT), "the document mode is unsplit only");
   // S is the q length (q tiles, lse/delta row base). The kv length sets the
   // row blocks, the strips and the workspace rows; it is S on the causal
   // path, where the extra argument is never read.
@@ -1580,10 +1732,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   const int DLTOFF = LSEOFF + BK_LSE_U16 * 2;
 
   const AttnStrips strips = attn_bwd_strips(
-      CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
+      MASK == ATTN_MASK_CAUSAL ? fold : ATTN_STRIPS_IDENTITY, kvb,
       __builtin_amdgcn_readfirstlane(wid), S_kv / 256);   // see dv
   const int kv0w = strips.kv0w;
   const int kvrow = kv0w + low;
+
+  int end = 0, emin = 0, emax = 0, qtn = S / 64;            // see dv
+  if constexpr (DOC) {
+    const int* endp = bounds + ((long)batch + b) * S;
+    end = attn_clampi(endp[kvrow], kvrow, S - 1);
+    attn_wave_minmax(end, emin, emax);
+    qtn = attn_doc_tiles_kv(endp[kvb * 256 + 255], kvb, S).last + 1;
+  }
 
   const u16* kptr = k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
   const u16* vptr = v + (long)b * v_sb + (long)hkv * v_sh + (long)kvrow * v_ss;
@@ -1598,7 +1758,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
   attn_zero(dkacc);
 
   const int qt0 = CAUSAL ? strips.qt0 : 0;
-  const int qtn = S / 64;
   const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
   uint4 qtst[2];
 
@@ -1685,8 +1844,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
       char* qtb = qb_ + QTOFF;
       const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
       const float* dltt = reinterpret_cast<const float*>(qb_ + DLTOFF);
-      const bool active = !CAUSAL || qt * 64 + 63 >= kv0w;
-      const bool need_mask = CAUSAL && qt * 64 < kv0w + 32;
+      const bool active =
+          !CAUSAL || (qt * 64 + 63 >= kv0w && (!DOC || qt * 64 <= emax));
+      const bool need_mask =
+          CAUSAL && (qt * 64 < kv0w + 32 || (DOC && qt * 64 + 63 > emin));
 
       AttnFrag pf[4];
       if (active) {
@@ -1710,7 +1871,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
           for (int r = 0; r < 16; ++r) {
             const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;
             float x = s[r] * scale2 - lse2t[sub * 32 + qr];
-            if (need_mask && qt * 64 + sub * 32 + qr < kvrow) x = -1e30f;
+            const int qa = qt * 64 + sub * 32 + qr;
+            if (need_mask && (qa < kvrow || (DOC && qa > end))) x = -1e30f;
             const float p = exp2_raw(x);
             s[r] = p * (dp[r] - dltt[sub * 32 + qr]) * scale;
           }
@@ -1758,8 +1920,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 
 // ---------------------------------------------------------------------------
 // dV and dK with PAIR ownership (attn_bwd_pair): causal, unsplit. Same grid,
-// staging and element arithmetic as attn_bwd_dv_kernel<true, false> and
-// attn_bwd_dk_kernel<true, false>; what differs is who computes what.
+// staging and element arithmetic as the causal unsplit attn_bwd_dv_kernel and
+// attn_bwd_dk_kernel; what differs is who computes what.
 //
 // Barriers: every wave reaches, per phase and q head, one barrier after the
 // first staging and two per tile (after the fragment exchange writes, and
@@ -2311,784 +2473,6 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(
   acc[1] = a1;
 }
 
-// ===========================================================================
-// Document-masked causal attention: the v7 forward and the dq/dv/dk kernels
-// under a per-token document mask. bounds is int32 [2, B, S]: bounds[0,b,s]
-// the window index of the first token of s's document (start), bounds[1,b,s]
-// that of its last (end). q sees kv iff start[q] <= kv <= q, which for valid
-// bounds (contiguous intervals, start and end constant on each) equals
-// kv <= q <= end[kv]. The mask is shared by all heads.
-//
-// Own kernels, so the causal ones above keep their instruction streams; tile
-// math, staging, ring and barriers are theirs. What differs:
-//   * fwd/dq: the lane owning q row qrow loads start once and masks
-//     kvr < start next to kvr > qrow. The kv walk begins at the workgroup-
-//     uniform tile attn_doc_tiles_q(start[b, qb*256], qb).first (ring slots,
-//     prologue and have2 count from there); a wave also sits out tiles wholly
-//     before the smallest start of its 32 rows, and masks every tile that
-//     some row's start cuts, not the diagonal band alone.
-//   * dv/dk: the lane owning kv row kvrow loads end once and masks q > end
-//     next to q < kvrow. The q walk stops at the workgroup-uniform tile
-//     attn_doc_tiles_kv(end[b, last row of the block], kvb, S).last. Strip
-//     ownership is the identity (256 neighbouring kv rows per workgroup),
-//     unsplit, no workspace: q ranges differ per document, so neither the
-//     fold nor the pair balances them (ROADMAP).
-//
-// Any int32 content is safe: a lane's start is clamped to [0, qrow], its end
-// to [kvrow, S-1], and both tile ranges are clamped below, so every address
-// derived from bounds stays inside the operands. Invalid bounds (not a
-// partition) give wrong numbers, never an out-of-range access.
-//
-// Forward and fully masked tiles. A row can meet tiles in which all its
-// entries are masked before its first real score: row 400 of a block whose
-// row 256 belongs to an earlier document, in a strip that also holds rows of
-// that document. Its masked scores are -1e30, so the first such tile sets
-// m_run = -1e30 (alpha 0 from -inf) and P = exp2(-1e30 - -1e30) = 1 on the
-// masked entries: l_run and oacc collect finite garbage. Further masked
-// tiles keep m_run (pm - m_run = 0). The first tile with a real score x has
-// x - m_run > 8, so the wave rescales, and alpha = exp2(-1e30 - x) is exactly
-// 0: garbage * 0 = 0, and from there masked entries give exp2(-1e30 - m) = 0
-// as in the causal kernel. That tile always comes because start <= qrow by
-// the clamp: every row sees its own diagonal entry. The rescale decision is
-// wave-wide (__all), so rows of two documents in one 32-row strip influence
-// each other's rounding (not their masks); the backward has no such coupling.
-// ===========================================================================
-
-struct AttnTiles { int first, last; };       // inclusive 64-row tile range
-
-__host__ __device__ __forceinline__ int attn_clampi(int x, int lo, int hi) {
-  return x < lo ? lo : (x > hi ? hi : x);
-}
-// kv tiles q block qb (256 rows) walks when its first row's document starts
-// at `start`: from that tile, at most the block's own first, to the diagonal
-__host__ __device__ __forceinline__ AttnTiles attn_doc_tiles_q(int start,
-                                                               int qb) {
-  AttnTiles t;
-  t.first = attn_clampi(start / 64, 0, qb * 4);
-  t.last = qb * 4 + 3;
-  return t;
-}
-// q tiles kv block kvb walks when its last row's document ends at `end`
-__host__ __device__ __forceinline__ AttnTiles attn_doc_tiles_kv(int end,
-                                                                int kvb,
-                                                                int S) {
-  AttnTiles t;
-  t.first = kvb * 4;
-  t.last = attn_clampi(end / 64 + 1, kvb * 4 + 1, S / 64) - 1;
-  return t;
-}
-
-// smallest and largest of a per-row value over the wave's 32 rows (lanes
-// low and low + 32 hold the same row), as wave-uniform scalars
-__device__ __forceinline__ void attn_wave_minmax(int x, int& lo, int& hi_) {
-  int mn = x, mx = x;
-#pragma unroll
-  for (int off = 1; off < 32; off <<= 1) {
-    mn = min(mn, __shfl_xor(mn, off, 64));
-    mx = max(mx, __shfl_xor(mx, off, 64));
-  }
-  lo = __builtin_amdgcn_readfirstlane(mn);
-  hi_ = __builtin_amdgcn_readfirstlane(mx);
-}
-
-__global__ __launch_bounds__(512) void attn_doc_fwd_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k,
-    const u16* __restrict__ v, u16* __restrict__ out,
-    float* __restrict__ lse, const int* __restrict__ bounds,
-    long q_sb, long q_sh, long q_ss,
-    long k_sb, long k_sh, long k_ss,
-    long v_sb, long v_sh, long v_ss,
-    long o_sb, long o_sh, long o_ss,
-    int n_heads, int gqa_group, int S, float scale2, int batch, int sched) {
-  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
-                                         sched);
-  const int qb = S / 256 - 1 - blk.rank;
-  const int h = blk.head;
-  const int b = blk.batch;
-  const int hkv = h / gqa_group;
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-  const int low = lane & 31;
-  const int hi = lane >> 5;
-
-  __shared__ __attribute__((aligned(16))) u16 lds[ATTN_RING_U16];
-
-  const int q0w = qb * 256 + wid * 32;
-  const int qrow = q0w + low;
-
-  const int* startp = bounds + (long)b * S;
-  const int start = attn_clampi(startp[qrow], 0, qrow);
-  int smin, smax;
-  attn_wave_minmax(start, smin, smax);
-  const AttnTiles tl = attn_doc_tiles_q(startp[qb * 256], qb);
-  const int t_begin = tl.first;
-  const int n_tiles = tl.last + 1 - t_begin;        // >= 4
-
-  AttnFrag qf[8];
-  attn_load_row(qf, q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss,
-                hi);
-
-  f32x16 oacc[4];
-  attn_zero(oacc);
-  float m_run = -INFINITY, l_run = 0.f;
-
-  AttnRingSrc src = attn_ring_src(
-      k + (long)b * k_sb + (long)hkv * k_sh + (long)t_begin * V6_BN * k_ss,
-      k_ss,
-      v + (long)b * v_sb + (long)hkv * v_sh + (long)t_begin * V6_BN * v_ss,
-      v_ss, tid);
-
-  // n_tiles >= 4: two tiles are always in flight after the prologue
-  attn_ring_issue(lds, 0, src);
-  attn_ring_issue(lds, 1, src);
-  v7_wait_vmcnt4();
-  v7_barrier();
-  attn_transpose(attn_ring_v(lds, 0), attn_ring_t(lds, 0), tid);
-  v7_barrier();
-
-  for (int t = 0; t < n_tiles; ++t) {          // t counts from t_begin
-    const int kv0 = (t_begin + t) * V6_BN;
-    const bool have2 = (t + 2) < n_tiles;
-    if (have2) attn_ring_issue(lds, (t + 2) % V7_RING, src);
-
-    char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
-    char* vtb = attn_ring_t(lds, t & 1);
-    const bool active = kv0 <= q0w + 31 && kv0 + V6_BN > smin;
-    const bool need_mask = kv0 + V6_BN > q0w || kv0 < smax;
-
-    f32x16 s0, s1;
-    AttnFrag pa[4];
-    float pm = -INFINITY;
-    if (active) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-#pragma unroll
-      for (int kc = 0; kc < 8; ++kc) {
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(low, kc * 16 + hi * 8)]);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kc].v, s0, 0, 0, 0);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(32 + low, kc * 16 + hi * 8)]);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kc].v, s1, 0, 0, 0);
-      }
-      if (need_mask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          float x0 = s0[r] * scale2;
-          if (kvr > qrow || kvr < start) x0 = -1e30f;
-          s0[r] = x0;
-          float x1 = s1[r] * scale2;
-          if (kvr + 32 > qrow || kvr + 32 < start) x1 = -1e30f;
-          s1[r] = x1;
-          pm = fmaxf(pm, fmaxf(x0, x1));
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] *= scale2;
-          s1[r] *= scale2;
-          pm = fmaxf(pm, fmaxf(s0[r], s1[r]));
-        }
-      }
-      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
-
-      // see the header: a row whose tiles so far were all masked sits at
-      // m_run = -1e30 and is rescaled by exactly 0 here at its first real one
-      if (!__all(pm - m_run <= 8.0f)) {
-        const float mn = fmaxf(m_run, pm);
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
-        m_run = mn;
-        l_run *= alpha;
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;
-      }
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p0 = exp2_raw(s0[r] - m_run);
-        const float p1 = exp2_raw(s1[r] - m_run);
-        s0[r] = p0;
-        s1[r] = p1;
-        psum += p0 + p1;
-      }
-      psum += __shfl_xor(psum, 32, 64);
-      l_run += psum;
-
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);
-        }
-      }
-
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) {
-          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-              &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-          oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              vf, pa[c].v, oacc[ds], 0, 0, 0);
-        }
-      }
-    }
-    if (t + 1 < n_tiles) {
-      if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
-      attn_transpose(attn_ring_v(lds, (t + 1) % V7_RING),
-                     attn_ring_t(lds, (t + 1) & 1), tid);
-    }
-    v7_barrier();
-  }
-
-  const float inv_l = 1.0f / l_run;
-  u16* orow = out + (long)b * o_sb + (long)h * o_sh + (long)qrow * o_ss;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 8 * g + 4 * hi + 32 * ds;
-      const unsigned w0 = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
-                                      oacc[ds][4 * g + 1] * inv_l);
-      const unsigned w1 = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
-                                      oacc[ds][4 * g + 3] * inv_l);
-      uint2 wv;
-      wv.x = w0;
-      wv.y = w1;
-      *reinterpret_cast<uint2*>(orow + d0) = wv;
-    }
-  }
-  if (hi == 0)
-    lse[((long)b * n_heads + h) * S + qrow] =
-        m_run * 0.6931471805599453f + __logf(l_run);
-}
-
-__global__ __launch_bounds__(512) void attn_doc_bwd_dq_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k,
-    const u16* __restrict__ v, const u16* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    u16* __restrict__ dq, const int* __restrict__ bounds,
-    long q_sb, long q_sh, long q_ss,
-    long k_sb, long k_sh, long k_ss,
-    long v_sb, long v_sh, long v_ss,
-    long do_sb, long do_sh, long do_ss,
-    long dq_sb, long dq_sh, long dq_ss,
-    int n_heads, int gqa_group, int S, float scale, int batch, int sched) {
-  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_heads, batch,
-                                         sched);
-  const int qb = S / 256 - 1 - blk.rank;
-  const int h = blk.head;
-  const int b = blk.batch;
-  const int hkv = h / gqa_group;
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-  const int low = lane & 31;
-  const int hi = lane >> 5;
-  const float scale2 = scale * ATTN_LOG2E;
-
-  __shared__ __attribute__((aligned(16))) u16 lds[ATTN_RING_U16];
-
-  const int q0w = qb * 256 + wid * 32;
-  const int qrow = q0w + low;
-
-  const int* startp = bounds + (long)b * S;
-  const int start = attn_clampi(startp[qrow], 0, qrow);
-  int smin, smax;
-  attn_wave_minmax(start, smin, smax);
-  const AttnTiles tl = attn_doc_tiles_q(startp[qb * 256], qb);
-  const int t_begin = tl.first;
-  const int n_tiles = tl.last + 1 - t_begin;        // >= 4
-
-  AttnFrag qf[8], dof[8];
-  attn_load_row(qf, q + (long)b * q_sb + (long)h * q_sh + (long)qrow * q_ss,
-                hi);
-  attn_load_row(dof, dout + (long)b * do_sb + (long)h * do_sh
-                         + (long)qrow * do_ss, hi);
-  const long lrow = ((long)b * n_heads + h) * S + qrow;
-  const float lse2 = lse[lrow] * ATTN_LOG2E;
-  const float dlt = delta[lrow];
-
-  f32x16 dqacc[4];
-  attn_zero(dqacc);
-
-  AttnRingSrc src = attn_ring_src(
-      k + (long)b * k_sb + (long)hkv * k_sh + (long)t_begin * V6_BN * k_ss,
-      k_ss,
-      v + (long)b * v_sb + (long)hkv * v_sh + (long)t_begin * V6_BN * v_ss,
-      v_ss, tid);
-
-  // n_tiles >= 4: two tiles are always in flight after the prologue
-  attn_ring_issue(lds, 0, src);
-  attn_ring_issue(lds, 1, src);
-  v7_wait_vmcnt4();
-  v7_barrier();
-  attn_transpose(attn_ring_k(lds, 0), attn_ring_t(lds, 0), tid);
-  v7_barrier();
-
-  for (int t = 0; t < n_tiles; ++t) {          // t counts from t_begin
-    const int kv0 = (t_begin + t) * V6_BN;
-    const bool have2 = (t + 2) < n_tiles;
-    if (have2) attn_ring_issue(lds, (t + 2) % V7_RING, src);
-
-    char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
-    char* vb = reinterpret_cast<char*>(attn_ring_v(lds, t % V7_RING));
-    char* ktb = attn_ring_t(lds, t & 1);
-    const bool active = kv0 <= q0w + 31 && kv0 + V6_BN > smin;
-    const bool need_mask = kv0 + V6_BN > q0w || kv0 < smax;
-
-    AttnFrag pds[4];
-    if (active) {
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-        f32x16 sx, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { sx[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-          bf16x8 a = *reinterpret_cast<const bf16x8*>(
-              &kb[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
-          sx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[kc].v, sx,
-                                                       0, 0, 0);
-          bf16x8 a2 = *reinterpret_cast<const bf16x8*>(
-              &vb[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, dof[kc].v, dp,
-                                                       0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float x = sx[r] * scale2 - lse2;
-          if (need_mask) {
-            const int kvr = kv0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (kvr > qrow || kvr < start) x = -1e30f;
-          }
-          const float p = exp2_raw(x);
-          sx[r] = p * (dp[r] - dlt) * scale;
-        }
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc)
-          pds[sub * 2 + cc].v = attn_repack(sx, cc * 8);
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) {
-          bf16x8 kf = *reinterpret_cast<const bf16x8*>(
-              &ktb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-          dqacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              kf, pds[c].v, dqacc[ds], 0, 0, 0);
-        }
-      }
-    }
-    if (t + 1 < n_tiles) {
-      if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
-      attn_transpose(attn_ring_k(lds, (t + 1) % V7_RING),
-                     attn_ring_t(lds, (t + 1) & 1), tid);
-    }
-    v7_barrier();
-  }
-
-  u16* dqrow = dq + (long)b * dq_sb + (long)h * dq_sh + (long)qrow * dq_ss;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dqrow, dqacc[ds], ds, hi);
-}
-
-// the staging of attn_bwd_dv_kernel / attn_bwd_dk_kernel, repeated for the
-// same reason as in the pair kernels (profiles/r09_attention_refactor.md)
-__global__ __launch_bounds__(512) void attn_doc_bwd_dv_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k,
-    const u16* __restrict__ dout, const float* __restrict__ lse,
-    u16* __restrict__ dv, const int* __restrict__ bounds,
-    long q_sb, long q_sh, long q_ss,
-    long k_sb, long k_sh, long k_ss,
-    long do_sb, long do_sh, long do_ss,
-    long dv_sb, long dv_sh, long dv_ss,
-    int n_heads, int n_kv_heads, int S, float scale, int batch, int sched) {
-  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_kv_heads,
-                                         batch, sched);
-  const int kvb = blk.rank;
-  const int gqa_group = n_heads / n_kv_heads;
-  const int hkv = blk.head;
-  const int b = blk.batch;
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-  const int low = lane & 31;
-  const int hi = lane >> 5;
-  const float scale2 = scale * ATTN_LOG2E;
-
-  __shared__ __attribute__((aligned(16))) u16 lds[2][BV_BUF_U16];
-  char* lds0 = reinterpret_cast<char*>(&lds[0][0]);
-  char* lds1 = reinterpret_cast<char*>(&lds[1][0]);
-  const int DOTOFF = BV_Q_U16 * 2;
-  const int LSEOFF = (BV_Q_U16 + BV_DOT_U16) * 2;
-
-  const AttnStrips strips = attn_bwd_strips(
-      ATTN_STRIPS_IDENTITY, kvb, __builtin_amdgcn_readfirstlane(wid), S / 256);
-  const int kv0w = strips.kv0w;
-  const int kvrow = kv0w + low;
-
-  const int* endp = bounds + ((long)batch + b) * S;
-  const int end = attn_clampi(endp[kvrow], kvrow, S - 1);
-  int emin, emax;
-  attn_wave_minmax(end, emin, emax);
-  const AttnTiles tl = attn_doc_tiles_kv(endp[kvb * 256 + 255], kvb, S);
-  const int qt0 = tl.first;
-  const int qtn = tl.last + 1;                // one past the last q tile
-
-  const u16* kptr = k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
-  AttnFrag kf[8];
-#pragma unroll
-  for (int kc = 0; kc < 8; ++kc)
-    kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
-
-  f32x16 dvacc[4];
-  attn_zero(dvacc);
-
-  const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  uint4 dtst[2];
-
-  for (int g = 0; g < gqa_group; ++g) {
-    const int h = hkv * gqa_group + g;
-    const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
-    const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
-    const float* lbase = lse + ((long)b * n_heads + h) * S;
-
-    const u16* qgp[2];
-    const u16* dtp[2];
-    {
-      const int idx0 = tid, idx1 = 512 + tid;
-      const int L0 = idx0 * 16, L1 = idx1 * 16;
-      const int r0 = L0 >> 8, r1 = L1 >> 8;
-      const int in0 = (((L0 & 255) ^ ((r0 & 15) << 4)) >> 1);
-      const int in1 = (((L1 & 255) ^ ((r1 & 15) << 4)) >> 1);
-      qgp[0] = qbase + (long)(qt0 * 64 + r0) * q_ss + in0;
-      qgp[1] = qbase + (long)(qt0 * 64 + r1) * q_ss + in1;
-      const int rp2 = (tid >> 4) * 2;
-      const int c8 = (tid & 15) * 8;
-      dtp[0] = dobase + (long)(qt0 * 64 + rp2) * do_ss + c8;
-      dtp[1] = dobase + (long)(qt0 * 64 + rp2 + 1) * do_ss + c8;
-    }
-    const long qstep = (long)64 * q_ss;
-    const long dostep = (long)64 * do_ss;
-
-#define BV_STAGE_IN(BUFI, QT)                                               \
-    {                                                                       \
-      _Pragma("unroll")                                                     \
-      for (int i = 0; i < 2; ++i) {                                         \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
-            16, 0, 0);                                                      \
-        qgp[i] += qstep;                                                    \
-      }                                                                     \
-      dtst[0] = *reinterpret_cast<const uint4*>(dtp[0]);                    \
-      dtst[1] = *reinterpret_cast<const uint4*>(dtp[1]);                    \
-      dtp[0] += dostep;                                                     \
-      dtp[1] += dostep;                                                     \
-      if (tid < 64)                                                         \
-        *reinterpret_cast<float*>(                                          \
-            &lds[BUFI][LSEOFF / 2 + tid * 2]) =                             \
-            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
-    }
-#define BV_WRITE_DOT(BUF)                                                   \
-    {                                                                       \
-      const int rp2_ = (tid >> 4) * 2;                                      \
-      const int c8_ = (tid & 15) * 8;                                       \
-      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
-      va_.u4 = dtst[0];                                                     \
-      vb_.u4 = dtst[1];                                                     \
-      _Pragma("unroll")                                                     \
-      for (int j = 0; j < 8; ++j) {                                         \
-        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
-        *reinterpret_cast<u32*>(&(BUF)[DOTOFF + vt_byte(c8_ + j, rp2_)]) =  \
-            pair_;                                                          \
-      }                                                                     \
-    }
-
-    BV_STAGE_IN(0, qt0)
-    BV_WRITE_DOT(lds0)
-    __syncthreads();
-
-    int cur = 0;
-    for (int qt = qt0; qt < qtn; ++qt) {
-      const bool have_next = (qt + 1) < qtn;
-      if (have_next) BV_STAGE_IN(cur ^ 1, qt + 1)
-
-      char* qb_ = cur ? lds1 : lds0;
-      char* dob = qb_ + DOTOFF;
-      const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
-      // this wave's kv rows need kv0w <= q <= the largest end of its rows
-      const bool active = qt * 64 + 63 >= kv0w && qt * 64 <= emax;
-      const bool need_mask = qt * 64 < kv0w + 32 || qt * 64 + 63 > emin;
-
-      AttnFrag pf[4];
-      if (active) {
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-          f32x16 s;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-          for (int kc = 0; kc < 8; ++kc) {
-            bf16x8 a = *reinterpret_cast<const bf16x8*>(
-                &qb_[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kc].v, s,
-                                                        0, 0, 0);
-          }
-          // P = 2^(s*scale2 - lse2[q]); mask q < kv and q > end
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;   // q within sub
-            float x = s[r] * scale2 - lse2t[sub * 32 + qr];
-            const int qa = qt * 64 + sub * 32 + qr;
-            if (need_mask && (qa < kvrow || qa > end)) x = -1e30f;
-            s[r] = exp2_raw(x);
-          }
-#pragma unroll
-          for (int cc = 0; cc < 2; ++cc) {
-            pf[sub * 2 + cc].v = attn_repack(s, cc * 8);
-          }
-        }
-      }
-      if (have_next) {
-        char* nb = cur ? lds0 : lds1;
-        BV_WRITE_DOT(nb)
-      }
-      if (active) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int ds = 0; ds < 4; ++ds) {
-            bf16x8 af = *reinterpret_cast<const bf16x8*>(
-                &dob[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-            dvacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                af, pf[c].v, dvacc[ds], 0, 0, 0);
-          }
-        }
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-
-  u16* dvrow = dv + (long)b * dv_sb + (long)hkv * dv_sh + (long)kvrow * dv_ss;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dvrow, dvacc[ds], ds, hi);
-}
-#undef BV_STAGE_IN
-#undef BV_WRITE_DOT
-
-__global__ __launch_bounds__(512) void attn_doc_bwd_dk_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k,
-    const u16* __restrict__ v, const u16* __restrict__ dout,
-    const float* __restrict__ lse, const float* __restrict__ delta,
-    u16* __restrict__ dk, const int* __restrict__ bounds,
-    long q_sb, long q_sh, long q_ss,
-    long k_sb, long k_sh, long k_ss,
-    long v_sb, long v_sh, long v_ss,
-    long do_sb, long do_sh, long do_ss,
-    long dk_sb, long dk_sh, long dk_ss,
-    int n_heads, int n_kv_heads, int S, float scale, int batch, int sched) {
-  const AttnBlock blk = attn_sched_block(blockIdx.x, S / 256, n_kv_heads,
-                                         batch, sched);
-  const int kvb = blk.rank;
-  const int gqa_group = n_heads / n_kv_heads;
-  const int hkv = blk.head;
-  const int b = blk.batch;
-  const int tid = threadIdx.x;
-  const int wid = tid >> 6;
-  const int lane = tid & 63;
-  const int low = lane & 31;
-  const int hi = lane >> 5;
-  const float scale2 = scale * ATTN_LOG2E;
-
-  __shared__ __attribute__((aligned(16))) u16 lds[2][BK_BUF_U16];
-  char* lds0 = reinterpret_cast<char*>(&lds[0][0]);
-  char* lds1 = reinterpret_cast<char*>(&lds[1][0]);
-  const int DOOFF = BK_Q_U16 * 2;
-  const int QTOFF = (BK_Q_U16 + BK_DO_U16) * 2;
-  const int LSEOFF = (BK_Q_U16 + BK_DO_U16 + BK_QT_U16) * 2;
-  const int DLTOFF = LSEOFF + BK_LSE_U16 * 2;
-
-  const AttnStrips strips = attn_bwd_strips(
-      ATTN_STRIPS_IDENTITY, kvb, __builtin_amdgcn_readfirstlane(wid), S / 256);
-  const int kv0w = strips.kv0w;
-  const int kvrow = kv0w + low;
-
-  const int* endp = bounds + ((long)batch + b) * S;
-  const int end = attn_clampi(endp[kvrow], kvrow, S - 1);
-  int emin, emax;
-  attn_wave_minmax(end, emin, emax);
-  const AttnTiles tl = attn_doc_tiles_kv(endp[kvb * 256 + 255], kvb, S);
-  const int qt0 = tl.first;
-  const int qtn = tl.last + 1;                // one past the last q tile
-
-  const u16* kptr = k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
-  const u16* vptr = v + (long)b * v_sb + (long)hkv * v_sh + (long)kvrow * v_ss;
-  AttnFrag kf[8], vf[8];
-#pragma unroll
-  for (int kc = 0; kc < 8; ++kc) {
-    kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
-    vf[kc].u = *reinterpret_cast<const uint4*>(vptr + kc * 16 + hi * 8);
-  }
-
-  f32x16 dkacc[4];
-  attn_zero(dkacc);
-
-  const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
-  uint4 qtst[2];
-
-  for (int g = 0; g < gqa_group; ++g) {
-    const int h = hkv * gqa_group + g;
-    const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
-    const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
-    const float* lbase = lse + ((long)b * n_heads + h) * S;
-    const float* dbase = delta + ((long)b * n_heads + h) * S;
-
-    const u16* qgp[2];
-    const u16* dgp[2];
-    const u16* qtp[2];
-    {
-      const int idx0 = tid, idx1 = 512 + tid;
-      const int L0 = idx0 * 16, L1 = idx1 * 16;
-      const int r0 = L0 >> 8, r1 = L1 >> 8;
-      const int in0 = (((L0 & 255) ^ ((r0 & 15) << 4)) >> 1);
-      const int in1 = (((L1 & 255) ^ ((r1 & 15) << 4)) >> 1);
-      qgp[0] = qbase + (long)(qt0 * 64 + r0) * q_ss + in0;
-      qgp[1] = qbase + (long)(qt0 * 64 + r1) * q_ss + in1;
-      dgp[0] = dobase + (long)(qt0 * 64 + r0) * do_ss + in0;
-      dgp[1] = dobase + (long)(qt0 * 64 + r1) * do_ss + in1;
-      const int rp2 = (tid >> 4) * 2;
-      const int c8 = (tid & 15) * 8;
-      qtp[0] = qbase + (long)(qt0 * 64 + rp2) * q_ss + c8;
-      qtp[1] = qbase + (long)(qt0 * 64 + rp2 + 1) * q_ss + c8;
-    }
-    const long qstep = (long)64 * q_ss;
-    const long dostep = (long)64 * do_ss;
-
-#define BK_STAGE_IN(BUFI, QT)                                               \
-    {                                                                       \
-      _Pragma("unroll")                                                     \
-      for (int i = 0; i < 2; ++i) {                                         \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
-            16, 0, 0);                                                      \
-        qgp[i] += qstep;                                                    \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)dgp[i],                                             \
-            (u32*)&lds[BUFI][DOOFF / 2 + (i * 512 + wu64 * 64) * 8],        \
-            16, 0, 0);                                                      \
-        dgp[i] += dostep;                                                   \
-      }                                                                     \
-      qtst[0] = *reinterpret_cast<const uint4*>(qtp[0]);                    \
-      qtst[1] = *reinterpret_cast<const uint4*>(qtp[1]);                    \
-      qtp[0] += qstep;                                                      \
-      qtp[1] += qstep;                                                      \
-      if (tid < 64)                                                         \
-        *reinterpret_cast<float*>(&lds[BUFI][LSEOFF / 2 + tid * 2]) =       \
-            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
-      else if (tid < 128)                                                   \
-        *reinterpret_cast<float*>(                                          \
-            &lds[BUFI][DLTOFF / 2 + (tid - 64) * 2]) =                      \
-            dbase[(QT) * 64 + tid - 64];                                    \
-    }
-#define BK_WRITE_QT(BUF)                                                    \
-    {                                                                       \
-      const int rp2_ = (tid >> 4) * 2;                                      \
-      const int c8_ = (tid & 15) * 8;                                       \
-      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
-      va_.u4 = qtst[0];                                                     \
-      vb_.u4 = qtst[1];                                                     \
-      _Pragma("unroll")                                                     \
-      for (int j = 0; j < 8; ++j) {                                         \
-        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
-        *reinterpret_cast<u32*>(&(BUF)[QTOFF + vt_byte(c8_ + j, rp2_)]) =   \
-            pair_;                                                          \
-      }                                                                     \
-    }
-
-    BK_STAGE_IN(0, qt0)
-    BK_WRITE_QT(lds0)
-    __syncthreads();
-
-    int cur = 0;
-    for (int qt = qt0; qt < qtn; ++qt) {
-      const bool have_next = (qt + 1) < qtn;
-      if (have_next) BK_STAGE_IN(cur ^ 1, qt + 1)
-
-      char* qb_ = cur ? lds1 : lds0;
-      char* dob = qb_ + DOOFF;
-      char* qtb = qb_ + QTOFF;
-      const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
-      const float* dltt = reinterpret_cast<const float*>(qb_ + DLTOFF);
-      const bool active = qt * 64 + 63 >= kv0w && qt * 64 <= emax;
-      const bool need_mask = qt * 64 < kv0w + 32 || qt * 64 + 63 > emin;
-
-      AttnFrag pf[4];
-      if (active) {
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-          f32x16 s, dp;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-          for (int kc = 0; kc < 8; ++kc) {
-            bf16x8 a = *reinterpret_cast<const bf16x8*>(
-                &qb_[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kc].v, s,
-                                                        0, 0, 0);
-            bf16x8 a2 = *reinterpret_cast<const bf16x8*>(
-                &dob[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, vf[kc].v, dp,
-                                                         0, 0, 0);
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            float x = s[r] * scale2 - lse2t[sub * 32 + qr];
-            const int qa = qt * 64 + sub * 32 + qr;
-            if (need_mask && (qa < kvrow || qa > end)) x = -1e30f;
-            const float p = exp2_raw(x);
-            s[r] = p * (dp[r] - dltt[sub * 32 + qr]) * scale;
-          }
-#pragma unroll
-          for (int cc = 0; cc < 2; ++cc) {
-            pf[sub * 2 + cc].v = attn_repack(s, cc * 8);
-          }
-        }
-      }
-      if (have_next) {
-        char* nb = cur ? lds0 : lds1;
-        BK_WRITE_QT(nb)
-      }
-      if (active) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-          for (int ds = 0; ds < 4; ++ds) {
-            bf16x8 af = *reinterpret_cast<const bf16x8*>(
-                &qtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-            dkacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                af, pf[c].v, dkacc[ds], 0, 0, 0);
-          }
-        }
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-
-  u16* dkrow = dk + (long)b * dk_sb + (long)hkv * dk_sh + (long)kvrow * dk_ss;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dkrow, dkacc[ds], ds, hi);
-}
-#undef BK_STAGE_IN
-#undef BK_WRITE_QT
-
 // batch / head / row strides of one [B, heads, S, 128] operand (elements)
 struct AttnStride { long sb, sh, ss; };
 // the three strides as consecutive kernel arguments
@@ -3157,14 +2541,14 @@ static int launch_fwd_v7(void* stream, const void* q, const void* k,
   if (!attn_grid_ok(S, n_heads, batch) || (causal && S_kv != S)) return -1;
   const float scale2 = scale * ATTN_LOG2E;   // fold log2(e)
   dim3 grid((S / 256) * n_heads * batch), block(512);
-  hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<true>
-                            : attn_fwd_v7_kernel<false>, grid, block, 0,
+  hipLaunchKernelGGL(causal ? attn_fwd_v7_kernel<ATTN_MASK_CAUSAL>
+                            : attn_fwd_v7_kernel<ATTN_MASK_NONE>, grid, block, 0,
                      reinterpret_cast<hipStream_t>(stream),
                      (const u16*)q, (const u16*)k, (const u16*)v,
                      (u16*)out, (float*)lse, ATTN_S3(qs), ATTN_S3(ks),
                      ATTN_S3(vs), ATTN_S3(os), n_heads,
                      n_heads / n_kv_heads, S, scale2, batch,
-                     attn_sched_mode(), S_kv);
+                     attn_sched_mode(), S_kv, (const int*)nullptr);
   return 0;
 }
 
@@ -3443,10 +2827,12 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                             AttnStride dvs, int batch, int n_heads,
                             int n_kv_heads, int S, int S_kv, float scale,
                             void* ws) {
+  constexpr int MASK = CAUSAL ? ATTN_MASK_CAUSAL : ATTN_MASK_NONE;
+  const int* const no_bounds = nullptr;
   const int sched = attn_sched_mode();
   {
     dim3 grid((S / 256) * n_heads * batch), block(512);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<CAUSAL>, grid, block, 0, st,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<MASK>, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dq,
@@ -3454,7 +2840,7 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        ATTN_S3(vs), ATTN_S3(dos),
                        ATTN_S3(dqs),
                        n_heads, n_heads / n_kv_heads, S, scale, batch, sched,
-                       S_kv);
+                       S_kv, no_bounds);
   }
   const int nrb = S_kv / 256;
   const bool split = ws != nullptr;
@@ -3473,15 +2859,15 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        ATTN_S3(dos), ATTN_S3(dvs),
                        n_heads, n_kv_heads, S, scale, batch, sched);
   } else {
-    auto dv_kernel = split ? attn_bwd_dv_kernel<CAUSAL, true>
-                           : attn_bwd_dv_kernel<CAUSAL, false>;
+    auto dv_kernel = split ? attn_bwd_dv_kernel<MASK, true>
+                           : attn_bwd_dv_kernel<MASK, false>;
     hipLaunchKernelGGL(dv_kernel, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)dout,
                        (const float*)lse, (u16*)dv,
                        ATTN_S3(qs), ATTN_S3(ks),
                        ATTN_S3(dos), ATTN_S3(dvs),
                        n_heads, n_kv_heads, S, scale, ws_v, batch, sched,
-                       fold_v, S_kv);
+                       fold_v, S_kv, no_bounds);
   }
   if (fold_k == ATTN_STRIPS_PAIR) {
     hipLaunchKernelGGL(attn_bwd_dk_pair_kernel, grid, block, 0, st,
@@ -3493,8 +2879,8 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        ATTN_S3(dks),
                        n_heads, n_kv_heads, S, scale, batch, sched);
   } else {
-    auto dk_kernel = split ? attn_bwd_dk_kernel<CAUSAL, true>
-                           : attn_bwd_dk_kernel<CAUSAL, false>;
+    auto dk_kernel = split ? attn_bwd_dk_kernel<MASK, true>
+                           : attn_bwd_dk_kernel<MASK, false>;
     hipLaunchKernelGGL(dk_kernel, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
@@ -3503,7 +2889,7 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
                        ATTN_S3(vs), ATTN_S3(dos),
                        ATTN_S3(dks),
                        n_heads, n_kv_heads, S, scale, ws_k, batch, sched,
-                       fold_k, S_kv);
+                       fold_k, S_kv, no_bounds);
   }
   if (split) {
     const long n_rows = (long)batch * n_kv_heads * S_kv;
@@ -3910,12 +3296,13 @@ extern "C" int attn_doc_fwd_strided(void* stream, const void* q,
   const AttnStride qs = attn_stride_at(st, 0), ks = attn_stride_at(st, 1),
                    vs = attn_stride_at(st, 2), os = attn_stride_at(st, 3);
   dim3 grid((S / 256) * n_heads * batch), block(512);
-  hipLaunchKernelGGL(attn_doc_fwd_kernel, grid, block, 0,
+  hipLaunchKernelGGL(attn_fwd_v7_kernel<ATTN_MASK_DOC>, grid, block, 0,
                      reinterpret_cast<hipStream_t>(stream),
                      (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
-                     (float*)lse, bounds, ATTN_S3(qs), ATTN_S3(ks),
+                     (float*)lse, ATTN_S3(qs), ATTN_S3(ks),
                      ATTN_S3(vs), ATTN_S3(os), n_heads, n_heads / n_kv_heads,
-                     S, scale * ATTN_LOG2E, batch, attn_sched_mode());
+                     S, scale * ATTN_LOG2E, batch, attn_sched_mode(), S,
+                     bounds);
   return 0;
 }
 
@@ -3943,29 +3330,35 @@ static int launch_doc_bwd(void* stream, const void* q, const void* k,
   if (with_delta)
     launch_delta(hs, out, dout, delta, os, dos, batch, n_heads, S);
   if (parts & ATTN_PART_DQ) {
-    hipLaunchKernelGGL(attn_doc_bwd_dq_kernel,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<ATTN_MASK_DOC>,
                        dim3((S / 256) * n_heads * batch), dim3(512), 0, hs,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
-                       (const float*)delta, (u16*)dq, bounds, ATTN_S3(qs),
+                       (const float*)delta, (u16*)dq, ATTN_S3(qs),
                        ATTN_S3(ks), ATTN_S3(vs), ATTN_S3(dos), ATTN_S3(dqs),
-                       n_heads, n_heads / n_kv_heads, S, scale, batch, sched);
+                       n_heads, n_heads / n_kv_heads, S, scale, batch, sched,
+                       S, bounds);
   }
+  // unsplit, no workspace; the document mode does not read the strip flag
   dim3 grid((S / 256) * n_kv_heads * batch), block(512);
   if (parts & ATTN_PART_DV) {
-    hipLaunchKernelGGL(attn_doc_bwd_dv_kernel, grid, block, 0, hs,
+    hipLaunchKernelGGL((attn_bwd_dv_kernel<ATTN_MASK_DOC, false>), grid,
+                       block, 0, hs,
                        (const u16*)q, (const u16*)k, (const u16*)dout,
-                       (const float*)lse, (u16*)dv, bounds, ATTN_S3(qs),
+                       (const float*)lse, (u16*)dv, ATTN_S3(qs),
                        ATTN_S3(ks), ATTN_S3(dos), ATTN_S3(dvs), n_heads,
-                       n_kv_heads, S, scale, batch, sched);
+                       n_kv_heads, S, scale, (float*)nullptr, batch, sched,
+                       ATTN_STRIPS_IDENTITY, S, bounds);
   }
   if (parts & ATTN_PART_DK) {
-    hipLaunchKernelGGL(attn_doc_bwd_dk_kernel, grid, block, 0, hs,
+    hipLaunchKernelGGL((attn_bwd_dk_kernel<ATTN_MASK_DOC, false>), grid,
+                       block, 0, hs,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
-                       (const float*)delta, (u16*)dk, bounds, ATTN_S3(qs),
+                       (const float*)delta, (u16*)dk, ATTN_S3(qs),
                        ATTN_S3(ks), ATTN_S3(vs), ATTN_S3(dos), ATTN_S3(dks),
-                       n_heads, n_kv_heads, S, scale, batch, sched);
+                       n_heads, n_kv_heads, S, scale, (float*)nullptr, batch,
+                       sched, ATTN_STRIPS_IDENTITY, S, bounds);
   }
   return 0;
 }
@@ -4005,7 +3398,8 @@ extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
   if (!st || !attn_strides_ok(st, 24)) return -1;
   // A launcher of its own, so that no benchmark switch sits in
   // launch_bwd_core: the causal unsplit launch of that one kernel, with the
-  // ownership launch_bwd_core would pick (attn_bwd_use_fold).
+  // ownership launch_bwd_core would pick (attn_bwd_use_fold). bounds is null
+  // from here on.
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
   const AttnStride qs = attn_stride_at(st, 0), ks = attn_stride_at(st, 1),
                    vs = attn_stride_at(st, 2), dos = attn_stride_at(st, 4),
@@ -4014,14 +3408,14 @@ extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
   const int sched = attn_sched_mode();
   dim3 grid((S / 256) * n_kv_heads * batch), block(512);
   if (part == ATTN_PART_DQ) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<ATTN_MASK_CAUSAL>,
                        dim3((S / 256) * n_heads * batch), block, 0, hs,
                        (const u16*)q, (const u16*)k, (const u16*)v,
                        (const u16*)dout, (const float*)lse,
                        (const float*)delta, (u16*)dq, ATTN_S3(qs),
                        ATTN_S3(ks), ATTN_S3(vs), ATTN_S3(dos), ATTN_S3(dqs),
                        n_heads, n_heads / n_kv_heads, S, scale, batch, sched,
-                       S);
+                       S, bounds);
   } else if (part == ATTN_PART_DV) {
     const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true,
                                        false, ATTN_BWD_DV);
@@ -4032,12 +3426,13 @@ extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
                          ATTN_S3(ks), ATTN_S3(dos), ATTN_S3(dvs), n_heads,
                          n_kv_heads, S, scale, batch, sched);
     else
-      hipLaunchKernelGGL((attn_bwd_dv_kernel<true, false>), grid, block, 0,
+      hipLaunchKernelGGL((attn_bwd_dv_kernel<ATTN_MASK_CAUSAL, false>), grid,
+                         block, 0,
                          hs, (const u16*)q, (const u16*)k, (const u16*)dout,
                          (const float*)lse, (u16*)dv, ATTN_S3(qs),
                          ATTN_S3(ks), ATTN_S3(dos), ATTN_S3(dvs), n_heads,
                          n_kv_heads, S, scale, (float*)nullptr, batch, sched,
-                         fold, S);
+                         fold, S, bounds);
   } else {
     const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true,
                                        false, ATTN_BWD_DK);
@@ -4049,13 +3444,14 @@ extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
                          ATTN_S3(ks), ATTN_S3(vs), ATTN_S3(dos), ATTN_S3(dks),
                          n_heads, n_kv_heads, S, scale, batch, sched);
     else
-      hipLaunchKernelGGL((attn_bwd_dk_kernel<true, false>), grid, block, 0,
+      hipLaunchKernelGGL((attn_bwd_dk_kernel<ATTN_MASK_CAUSAL, false>), grid,
+                         block, 0,
                          hs, (const u16*)q, (const u16*)k, (const u16*)v,
                          (const u16*)dout, (const float*)lse,
                          (const float*)delta, (u16*)dk, ATTN_S3(qs),
                          ATTN_S3(ks), ATTN_S3(vs), ATTN_S3(dos), ATTN_S3(dks),
                          n_heads, n_kv_heads, S, scale, (float*)nullptr,
-                         batch, sched, fold, S);
+                         batch, sched, fold, S, bounds);
   }
   return 0;
 }
