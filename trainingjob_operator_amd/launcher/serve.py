@@ -6,7 +6,7 @@ families an OpenAI-ish token-in/token-out endpoint on an MI355X node:
 
     python -m trainingjob_operator_amd.launcher.serve \
         --model llama3-8b --port 8000 [--ckpt-dir DIR] [--graph]
-        [--paged [--max-slots N] [--pool-pages N]]
+        [--paged [--max-slots N] [--pool-pages N] [--prefill-chunk N]]
 
 The API is deliberately token-level (``prompt_tokens`` → ``tokens``):
 tokenizers are workload assets the cluster may not have offline, and the
@@ -20,6 +20,9 @@ With --paged the sequences of all requests share one paged KV cache and
 one decode loop instead (models/paged.PagedEngine): prompts of different
 lengths are accepted, every sequence is its own engine request, and
 concurrent HTTP requests share decode steps rather than queueing.
+--prefill-chunk N (N > 0) also prefills inside the engine, straight into
+the pages, at most N prompt tokens per step; 0 (default) prefills every
+request at once on a temporary contiguous cache.
 
 Endpoints:
     GET  /healthz   liveness + model name
@@ -46,11 +49,14 @@ _PAGED_GAUGES = {}
 
 
 def create_app(model, model_name: str = "model", paged: bool = False,
-               max_slots: int = 8, pool_pages: Optional[int] = None):
+               max_slots: int = 8, pool_pages: Optional[int] = None,
+               prefill_chunk: int = 0):
     """Build the FastAPI app around an already-constructed model (tests
     pass a CPU llama-tiny; the CLI builds the named config on cuda:0).
     paged=True serves /generate through a PagedEngine of `max_slots`
-    sequences over `pool_pages` 64-row KV pages (default 32 per slot)."""
+    sequences over `pool_pages` 64-row KV pages (default 32 per slot);
+    prefill_chunk > 0 selects the engine's paged prefill with that many
+    prompt tokens per step."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -108,7 +114,9 @@ def create_app(model, model_name: str = "model", paged: bool = False,
         model.eval()
         engine = PagedEngine(
             model, max_slots=max_slots, n_pages=pool_pages,
-            graph=os.environ.get("AITJ_DECODE_GRAPH") == "1")
+            graph=os.environ.get("AITJ_DECODE_GRAPH") == "1",
+            **({"prefill": "paged", "prefill_chunk": int(prefill_chunk)}
+               if prefill_chunk else {}))
         if mx:
             # shared like _METRICS; they follow the newest paged app
             from prometheus_client import Gauge
@@ -183,7 +191,9 @@ def create_app(model, model_name: str = "model", paged: bool = False,
         if engine is not None:
             body.update(paged=True, max_slots=engine.max_slots,
                         pages_total=engine.cache.n_pages,
-                        pages_free=engine.cache.pages_free)
+                        pages_free=engine.cache.pages_free,
+                        prefill_chunk=(engine.prefill_chunk
+                                       if engine.prefill == "paged" else 0))
         return body
 
     @app.get("/metrics")
@@ -311,6 +321,11 @@ def main(argv=None):
     ap.add_argument("--pool-pages", type=int, default=None,
                     help="64-row KV pages in the pool (with --paged; "
                          "default 32 per slot)")
+    ap.add_argument("--prefill-chunk", type=int, default=0,
+                    help="with --paged: prefill inside the engine, straight "
+                         "into the pages, at most N prompt tokens per step "
+                         "(0 = prefill each request at once on a contiguous "
+                         "cache)")
     args = ap.parse_args(argv)
     if args.graph:
         os.environ["AITJ_DECODE_GRAPH"] = "1"
@@ -321,7 +336,8 @@ def main(argv=None):
         step = load_model_only(args.ckpt_dir, model)
         print(f"loaded checkpoint step {step} from {args.ckpt_dir}")
     app = create_app(model, args.model, paged=args.paged,
-                     max_slots=args.max_slots, pool_pages=args.pool_pages)
+                     max_slots=args.max_slots, pool_pages=args.pool_pages,
+                     prefill_chunk=args.prefill_chunk)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 
 

@@ -17,6 +17,11 @@ device (ops.rope_cache_paged, ops.decode_attention_paged):
     ordinary _forward_cached, then load_prefix), decodes one token for
     every active slot and frees the slots of finished requests, which
     the next step refills. That refill is the continuous batching;
+  * _prefill_paged — the opt-in prefill (PagedEngine(prefill="paged")):
+    one packed forward over prompt chunks of several slots that writes
+    the pages directly (ops.rope_cache_paged_rows) and attends them
+    through the block table (ops.prefill_attention_paged), bounded per
+    step by prefill_chunk;
   * generate_ragged — prompts of different lengths in, one tensor each out.
 
 Admission reserves ceil((prompt + max_new_tokens) / 64) pages up front
@@ -35,7 +40,8 @@ from typing import Dict, List, Optional
 import torch
 
 from ..ops import (decode_attention_paged, decode_linear, fused_rmsnorm,
-                   reference, rope_cache_paged)
+                   prefill_attention_paged, prefill_work, reference,
+                   rope_cache_paged, rope_cache_paged_rows)
 from .generate import KVCache, _forward_cached, _mlp_cached, _sample
 
 PAGE_ROWS = reference.PAGE_ROWS
@@ -79,6 +85,9 @@ class PagedKVCache:
         self.owned: List[List[int]] = [[] for _ in range(max_slots)]
         self.reserved: List[int] = [0] * max_slots
         self.host_pos: List[int] = [-1] * max_slots
+        # prompt rows a slot under paged prefill holds so far; -1 = the
+        # slot is not prefilling (idle or decoding)
+        self.prefilled: List[int] = [-1] * max_slots
 
     # -- accounting ------------------------------------------------------
     @property
@@ -141,6 +150,7 @@ class PagedKVCache:
         self.free_pages.extend(reversed(self.owned[slot]))
         self.owned[slot] = []
         self.reserved[slot] = 0
+        self.prefilled[slot] = -1
         self.block_table[slot].zero_()
         self.set_pos(slot, -1)
 
@@ -171,7 +181,9 @@ class PagedKVCache:
         """Raise AssertionError unless the table is consistent: device
         table and positions equal the host mirror, entries in range, no
         page owned twice, no owned page on the free list, every page
-        accounted for, positions inside the owned pages."""
+        accounted for, positions inside the owned pages. A slot without a
+        position owns pages only while it is being prefilled, and then
+        exactly the pages of the rows prefilled so far."""
         table = self.block_table.cpu().tolist()
         pos = self.pos.cpu().tolist()
         seen = set()
@@ -187,8 +199,15 @@ class PagedKVCache:
             assert pos[s] <= len(own) * PAGE_ROWS \
                 and pos[s] < max(1, self.reserved[s]) * PAGE_ROWS, \
                 f"slot {s} pos {pos[s]} beyond its {len(own)} pages"
-            if pos[s] < 0:
+            if pos[s] < 0 and self.prefilled[s] >= 0:
+                assert len(own) == pages_for(self.prefilled[s]), \
+                    f"prefilling slot {s} owns {len(own)} pages for " \
+                    f"{self.prefilled[s]} rows"
+            elif pos[s] < 0:
                 assert not own, f"idle slot {s} owns pages"
+            else:
+                assert self.prefilled[s] < 0, \
+                    f"slot {s} decodes while marked prefilling"
             for j, page in enumerate(table[s][:len(own)]):
                 assert page == own[j], \
                     f"slot {s} page {j}: device {page} != host {own[j]}"
@@ -243,9 +262,67 @@ def _step_paged(model, cur: torch.Tensor,
     return logits.reshape(B, -1)
 
 
+@torch.no_grad()
+def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
+                   chunks, last_rows) -> torch.Tensor:
+    """One packed prefill forward straight into the pages: tokens [1, T]
+    are the concatenated chunks = [(slot, pos0, n_tokens), ...] of several
+    sequences, whose pages up to each chunk's last row the caller owns
+    (ensure_row). Every layer ropes q/k at the tokens' own positions and
+    writes k/v into the pages (ops.rope_cache_paged_rows), then attends
+    the cache rows 0..position through the block table
+    (ops.prefill_attention_paged). last_rows names the packed rows that
+    end a prompt; only those go through the final norm and lm_head:
+    returns logits [len(last_rows), V]. cache.pos is neither read nor
+    written: a slot stays idle for the decode step until the engine sets
+    its position."""
+    cfg = model.cfg
+    T = tokens.shape[1]
+    dev = tokens.device
+    scale = 1.0 / math.sqrt(cfg.head_dim)
+    work, tok_slot, tok_pos = prefill_work(chunks, dev)
+    assert tok_slot.numel() == T, (tok_slot.numel(), T)
+    x = model.embed(tokens)                                # [1, T, H]
+    residual = None
+    for li, blk in enumerate(model.blocks):
+        attn = blk.attn
+        normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
+                                         residual, cfg.norm_eps)
+        qkv = decode_linear(normed, attn.qkv_proj.weight)
+        q = rope_cache_paged_rows(qkv.reshape(T, -1), cache.k[li],
+                                  cache.v[li], model.inv_freq,
+                                  cache.block_table, tok_slot, tok_pos,
+                                  cfg.num_heads, cfg.num_kv_heads)
+        o = prefill_attention_paged(q, cache.k[li], cache.v[li],
+                                    cache.block_table, work, scale)
+        if o is None:                 # off-GPU or head_dim != 128: twin
+            o = reference.prefill_attention_paged(
+                q, cache.k[li], cache.v[li], cache.block_table, work, scale)
+        o = o.reshape(1, T, cfg.num_heads * cfg.head_dim).to(x.dtype)
+        attn_out = decode_linear(o, attn.o_proj.weight)
+        normed, residual = fused_rmsnorm(attn_out,
+                                         blk.post_attn_norm_weight,
+                                         residual, cfg.norm_eps)
+        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
+            else blk.moe(normed)
+    if not last_rows:                 # no prompt ends in this batch
+        return x.new_zeros(0, model.lm_head.weight.shape[0])
+    rows = torch.tensor(list(last_rows), dtype=torch.long, device=dev)
+    x = x[:, rows]
+    if residual is not None:
+        residual = residual[:, rows]
+    normed, _ = fused_rmsnorm(x.contiguous(), model.final_norm_weight,
+                              None if residual is None
+                              else residual.contiguous(), cfg.norm_eps)
+    logits = decode_linear(normed, model.lm_head.weight)
+    return logits.reshape(len(rows), -1)
+
+
 class PagedRequest:
     """One sequence in the engine. `tokens` grows from the prompt;
-    `done` is set when it finished (or failed: `error`)."""
+    `done` is set when it finished (or failed: `error`). With paged
+    prefill, `n_prefilled` counts the prompt tokens already in the pages
+    and `prefilling` holds until the whole prompt is."""
 
     def __init__(self, rid: int, prompt: List[int], max_new_tokens: int,
                  temperature: float, top_k: int, eos_token: Optional[int],
@@ -261,6 +338,9 @@ class PagedRequest:
         if seed is not None:
             self.generator = torch.Generator(device="cpu").manual_seed(seed)
         self.slot: Optional[int] = None
+        self.prefilling = False
+        self.n_prefilled = 0
+        self.admit_seq = -1           # admission order among prefilling slots
         self.error: Optional[BaseException] = None
         self.done = threading.Event()
 
@@ -287,12 +367,33 @@ class PagedEngine:
     host writes tokens, table rows and positions between replays. Like
     the contiguous decode graph it is opt-in and validated outside the
     test suite (scripts/graphcheck.py --paged).
+
+    prefill="contiguous" (default) prefills each admitted request at once
+    on a temporary batch-1 contiguous cache and pages the result in.
+    prefill="paged" admits a request as *prefilling* (slot taken, pages
+    reserved, device position still -1 so the decode step skips it) and
+    every step() packs up to `prefill_chunk` prompt tokens of the
+    prefilling slots, in admission order, into one _prefill_paged forward
+    that writes the pages directly: short prompts share a batch, a long
+    prompt spans several steps while the other slots keep decoding. A
+    prompt that completes gets its first token and joins the same step's
+    decode. Prefill always runs eagerly, between graph replays.
     """
 
     def __init__(self, model, max_slots: int = 8,
                  n_pages: Optional[int] = None,
                  max_pages_per_seq: Optional[int] = None,
-                 graph: bool = False):
+                 graph: bool = False, prefill: str = "contiguous",
+                 prefill_chunk: int = 512):
+        if prefill not in ("contiguous", "paged"):
+            raise ValueError(f"prefill must be 'contiguous' or 'paged', "
+                             f"not {prefill!r}")
+        if prefill == "paged" and prefill_chunk < 1:
+            raise ValueError("prefill_chunk must be >= 1")
+        self.prefill = prefill
+        self.prefill_chunk = int(prefill_chunk)
+        self.prefill_steps = 0
+        self._admit_seq = 0
         self.model = model
         self.device = model.embed.weight.device
         if n_pages is None:
@@ -422,6 +523,73 @@ class PagedEngine:
             else:
                 self._host_cur[slot] = tok
 
+    def _admit_paged(self) -> None:
+        """_admit's slot and reservation rule (arrival order, the same
+        cache.admit), without the prefill: the request is marked
+        prefilling and its slot's device position stays -1."""
+        for slot in range(self.max_slots):
+            if self.slots[slot] is not None:
+                continue
+            with self._lock:
+                if not self.queue:
+                    return
+                req = self.queue[0]
+                rows = req.prompt_len + req.max_new_tokens
+                if not self.cache.admit(slot, rows):
+                    return                     # wait for a release
+                self.queue.popleft()
+            req.slot = slot
+            req.prefilling = True
+            req.n_prefilled = 0
+            req.admit_seq = self._admit_seq
+            self._admit_seq += 1
+            self.slots[slot] = req
+            self.cache.prefilled[slot] = 0
+
+    def _prefill_step(self, finished: list) -> None:
+        """Up to prefill_chunk prompt tokens of the prefilling slots, in
+        admission order, through one packed _prefill_paged; prompts that
+        complete get their first token and their position."""
+        pending = sorted((r for r in self.slots
+                          if r is not None and r.prefilling),
+                         key=lambda r: r.admit_seq)
+        budget = self.prefill_chunk
+        chunks, toks, last_rows, completing = [], [], [], []
+        for req in pending:
+            if budget <= 0:
+                break
+            n = min(budget, req.prompt_len - req.n_prefilled)
+            p0 = req.n_prefilled
+            self.cache.ensure_row(req.slot, p0 + n - 1)
+            chunks.append((req.slot, p0, n))
+            toks.extend(req.tokens[p0:p0 + n])
+            budget -= n
+            if p0 + n == req.prompt_len:
+                last_rows.append(len(toks) - 1)
+                completing.append(req)
+        if not chunks:
+            return
+        tokens = torch.tensor([toks], dtype=torch.long, device=self.device)
+        logits = _prefill_paged(self.model, tokens, self.cache, chunks,
+                                last_rows)
+        self.prefill_steps += 1
+        for slot, p0, n in chunks:
+            self.slots[slot].n_prefilled = p0 + n
+            self.cache.prefilled[slot] = p0 + n
+        greedy = None
+        if any(r.temperature <= 0.0 for r in completing):
+            greedy = logits.argmax(dim=-1).tolist()        # one sync
+        for i, req in enumerate(completing):
+            tok = self._pick(req, logits[i], greedy[i] if greedy else None)
+            req.tokens.append(tok)
+            req.prefilling = False
+            self.cache.prefilled[req.slot] = -1
+            if req.finished:
+                self._retire(req, finished)
+            else:
+                self.cache.set_pos(req.slot, req.prompt_len)
+                self._host_cur[req.slot] = tok
+
     def _decode(self) -> torch.Tensor:
         self.cur.copy_(torch.tensor(self._host_cur, dtype=torch.long))
         if not self.graph_mode:
@@ -456,8 +624,13 @@ class PagedEngine:
         the requests that finished during this step."""
         finished: List[PagedRequest] = []
         try:
-            self._admit(finished)
-            active = [r for r in self.slots if r is not None]
+            if self.prefill == "paged":
+                self._admit_paged()
+                self._prefill_step(finished)
+            else:
+                self._admit(finished)
+            active = [r for r in self.slots
+                      if r is not None and not r.prefilling]
             if not active:
                 return finished
             for req in active:      # page for the row this step writes
@@ -497,6 +670,7 @@ class PagedEngine:
                     pass
                 self.slots[req.slot] = None
                 req.slot = None
+            req.prefilling = False
             req.done.set()
 
     def run(self) -> Dict[int, torch.Tensor]:
@@ -516,11 +690,15 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
                     eos_token: Optional[int] = None,
                     seed: Optional[int] = None, max_slots: int = 8,
                     n_pages: Optional[int] = None,
-                    graph: bool = False) -> List[torch.Tensor]:
+                    graph: bool = False,
+                    prefill_chunk: Optional[int] = None
+                    ) -> List[torch.Tensor]:
     """generate() for prompts of DIFFERENT lengths: every prompt is its
     own engine request (own position, own pages, own generator seeded
     with `seed`), decoded together `max_slots` at a time. Returns one
-    1-D tensor (prompt + generated) per prompt, in order."""
+    1-D tensor (prompt + generated) per prompt, in order. prefill_chunk:
+    None or 0 = prefill each prompt at once on a contiguous cache; N > 0 =
+    paged prefill, at most N prompt tokens per engine step."""
     was_training = model.training
     model.eval()
     try:
@@ -529,8 +707,10 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
         max_slots = max(1, min(max_slots, len(prompts)))
         if n_pages is None:
             n_pages = need * max_slots
+        paged = {"prefill": "paged", "prefill_chunk": int(prefill_chunk)} \
+            if prefill_chunk else {}
         eng = PagedEngine(model, max_slots=max_slots, n_pages=n_pages,
-                          max_pages_per_seq=need, graph=graph)
+                          max_pages_per_seq=need, graph=graph, **paged)
         ids = [eng.submit(p, max_new_tokens, temperature, top_k, eos_token,
                           seed) for p in prompts]
         done = eng.run()

@@ -17,7 +17,10 @@ from .functional import (
     gather_rows,
     make_inv_freq,
     moe_combine,
+    prefill_attention_paged,
+    prefill_work,
     rope_cache_paged,
+    rope_cache_paged_rows,
     swiglu,
     swiglu_packed,
 )
@@ -35,7 +38,10 @@ __all__ = [
     "fused_cross_entropy",
     "fused_rmsnorm",
     "make_inv_freq",
+    "prefill_attention_paged",
+    "prefill_work",
     "rope_cache_paged",
+    "rope_cache_paged_rows",
     "swiglu",
     "available",
     "build_ops",

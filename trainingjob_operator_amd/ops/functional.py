@@ -349,6 +349,113 @@ def rope_cache_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
     return q
 
 
+def rope_cache_paged_rows(qkv: torch.Tensor, k_pool: torch.Tensor,
+                          v_pool: torch.Tensor, inv_freq: torch.Tensor,
+                          block_table: torch.Tensor, tok_slot: torch.Tensor,
+                          tok_pos: torch.Tensor, num_heads: int,
+                          num_kv_heads: int) -> torch.Tensor:
+    """rope_cache_paged for T packed tokens of several sequences (hip/
+    ops.hip rope_cache_paged_rows): qkv [T, (nh+2*nkv)*D]; token t belongs
+    to block-table row tok_slot[t] (int32) and sits at cache position
+    tok_pos[t] (int64). Returns roped q [T, nh, D]; roped k and copied v
+    land in row tok_pos % 64 of page block_table[tok_slot][tok_pos // 64],
+    in place. A token with tok_pos < 0 writes no k/v and gets a zero q.
+    Off-GPU (or fp32) the torch reference does the same work."""
+    n_pages, _, R, D = k_pool.shape
+    T = qkv.shape[0]
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and k_pool.dtype == torch.bfloat16
+            and inv_freq.dtype == torch.float32
+            and R == reference.PAGE_ROWS):
+        return reference.rope_cache_paged_rows(
+            qkv, k_pool, v_pool, inv_freq, block_table, tok_slot, tok_pos,
+            num_heads, num_kv_heads)
+    assert k_pool.is_contiguous() and v_pool.is_contiguous()
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous()
+    assert tok_slot.dtype == torch.int32 and tok_slot.shape == (T,)
+    assert tok_pos.dtype == torch.int64 and tok_pos.shape == (T,)
+    assert tok_slot.is_contiguous() and tok_pos.is_contiguous()
+    assert k_pool.shape[1] == num_kv_heads
+    assert qkv.numel() == T * (num_heads + 2 * num_kv_heads) * D
+    lib = _hip()
+    qkv = qkv.contiguous()
+    q = torch.empty(T, num_heads, D, dtype=torch.bfloat16,
+                    device=qkv.device)
+    rc = lib.rope_cache_paged_rows(
+        native.stream_ptr(), _ptr(qkv), _ptr(q), _ptr(k_pool), _ptr(v_pool),
+        _ptr(inv_freq), _ptr(block_table), _ptr(tok_slot), _ptr(tok_pos),
+        T, block_table.shape[0], num_heads, num_kv_heads, n_pages,
+        block_table.shape[1], D)
+    native.check_rc(rc, "rope_cache_paged_rows", f"T={T} D={D}")
+    return q
+
+
+def prefill_work(chunks, device="cpu"):
+    """Host helper of the paged prefill: chunks = [(slot, pos0, n_tokens),
+    ...] in the order their tokens are packed -> (work, tok_slot, tok_pos).
+    work [n, 4] int32 rows (slot, q_row0, n_rows, pos0), every chunk cut
+    into blocks of at most 256 rows, heaviest (most kv tiles) first;
+    tok_slot [T] int32 and tok_pos [T] int64 name every packed token's
+    block-table row and cache position."""
+    rows, slots, poss = [], [], []
+    q_row = 0
+    for slot, pos0, n in chunks:
+        assert n > 0 and pos0 >= 0 and slot >= 0, (slot, pos0, n)
+        for off in range(0, n, reference.PREFILL_BLOCK_ROWS):
+            nr = min(reference.PREFILL_BLOCK_ROWS, n - off)
+            rows.append((slot, q_row + off, nr, pos0 + off))
+        slots.extend([slot] * n)
+        poss.extend(range(pos0, pos0 + n))
+        q_row += n
+    rows.sort(key=lambda r: -((r[3] + r[2] - 1) // reference.PAGE_ROWS))
+    work = torch.tensor(rows, dtype=torch.int32).reshape(-1, 4)
+    return (work.to(device),
+            torch.tensor(slots, dtype=torch.int32).to(device),
+            torch.tensor(poss, dtype=torch.int64).to(device))
+
+
+def prefill_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                            v_pool: torch.Tensor, block_table: torch.Tensor,
+                            work: torch.Tensor, scale: float,
+                            out: Optional[torch.Tensor] = None
+                            ) -> Optional[torch.Tensor]:
+    """Causal flash forward of packed prefill rows against a PAGED cache
+    (hip/attention.hip attn_prefill_paged): q [T, H, D] rows of several
+    sequences; work [n, 4] int32 (prefill_work) says which rows sit at
+    which cache positions of which block-table row. The row at position p
+    attends cache rows 0..p, which rope_cache_paged_rows has written.
+    Returns o [T, H, D] (rows no work row names are left unwritten; `out`
+    supplies the buffer), or None when the shape is unsupported (the
+    caller falls back to reference.prefill_attention_paged).
+    Inference-only."""
+    T, H, D = q.shape
+    n_pages, n_kv, R = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
+    G = H // n_kv if H % n_kv == 0 else 0
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and D == 128 and T > 0
+            and G >= 1 and R == reference.PAGE_ROWS and q.is_contiguous()
+            and k_pool.dtype == torch.bfloat16
+            and k_pool.shape == v_pool.shape
+            and k_pool.is_contiguous() and v_pool.is_contiguous()
+            and block_table.dtype == torch.int32
+            and block_table.dim() == 2 and block_table.is_contiguous()
+            and work.is_cuda and work.dtype == torch.int32
+            and work.dim() == 2 and work.shape[1] == 4
+            and work.shape[0] > 0 and work.is_contiguous()
+            and (out is None or (out.shape == q.shape
+                                 and out.dtype == q.dtype
+                                 and out.is_contiguous()))):
+        return None
+    lib = _hip()
+    o = torch.empty_like(q) if out is None else out
+    rc = lib.attn_prefill_paged(
+        native.stream_ptr(), _ptr(q), _ptr(k_pool), _ptr(v_pool), _ptr(o),
+        _ptr(block_table), _ptr(work), work.shape[0], T, H, n_kv,
+        block_table.shape[0], n_pages, block_table.shape[1], scale)
+    native.check_rc(rc, "attn_prefill_paged",
+                    f"T={T} H={H} n_kv={n_kv} blocks={work.shape[0]}")
+    return o
+
+
 def decode_swiglu(x: torch.Tensor,
                   gate_up_weight: torch.Tensor) -> Optional[torch.Tensor]:
     """silu(x @ Wg^T) * (x @ Wu^T) over the packed [2F, K] gate|up weight

@@ -352,6 +352,13 @@ __device__ __forceinline__ const u16* attn_glds_src(const u16* base, int row0,
   const int in = (((L & 255) ^ ((r & 15) << 4)) >> 1);
   return base + (long)(row0 + r) * ss + in;
 }
+// the same as an element offset into a contiguous [64, D] slab (one kv head
+// of one cache page): constant per lane, whatever page a tile comes from
+__device__ __forceinline__ int attn_glds_page_off(int L) {
+  const int r = L >> 8;
+  const int in = (((L & 255) ^ ((r & 15) << 4)) >> 1);
+  return r * ATTN_D + in;
+}
 
 // Issue a thread's two 16-byte glds for each of two 64-row images,
 // interleaved, and advance the sources one tile. A wave's 64 lanes land
@@ -1229,6 +1236,258 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
   if (hi == 0)
     lse[((long)b * n_heads + h) * S + qrow] =
         m_run * 0.6931471805599453f + __logf(l_run);
+}
+
+// ===========================================================================
+// Paged prefill forward: the causal v7 forward with queries at arbitrary
+// cache positions and K/V tiles found through a block table. A sibling of
+// attn_fwd_v7_kernel built from the same pieces (attn_load_row, the ring,
+// attn_transpose, the S/softmax/PV body, statement for statement), so the v7
+// instantiations keep their instruction streams.
+//
+// q and out are packed rows [T, H, 128]; the pools are [n_pages, n_kv, 64,
+// 128], table [B, max_pages] int32 as in the paged decode kernels. A cache
+// page is 64 rows = one kv tile = one ring slot, and a kv head of a page is a
+// contiguous [64, 128] slab: a lane's in-tile glds offset is constant
+// (attn_glds_page_off) and only the wave-uniform slab base changes per tile.
+//
+// Grid n_blocks * H. Block i reads work[i] = (slot, q_row0, n_rows, pos0):
+// rows q_row0 .. q_row0 + n_rows - 1 (n_rows <= 256) of q/out belong to
+// block-table row `slot` and sit at cache positions pos0 .. pos0 + n_rows - 1
+// (pos0 need not be a multiple of 64). Row r attends cache rows 0 .. pos0 + r;
+// the walk is tiles 0 .. (pos0 + n_rows - 1) / 64. The stale rows of a last
+// page lie beyond every position, so the causal mask covers them.
+//
+// The table entry of a tile is a wave-uniform scalar load, fetched one tile
+// ahead of the issue that needs it (the entry for tile t + 3 during tile t),
+// so no glds waits on a dependent scalar load.
+//
+// Rows beyond n_rows: such a lane carries the block's LAST valid row (same q,
+// same position), takes part in every barrier and in the wave-wide rescale
+// decision and stores nothing, so the output is a function of the valid
+// inputs only. A wave without any valid row skips the MFMAs and keeps
+// staging and the barriers.
+//
+// Every descriptor field is clamped before use (attn_prefill_clamp) and every
+// table entry into [0, n_pages), so any int32 content of work and table is
+// memory-safe; only valid content gives meaningful numbers. No lse is
+// written. With the whole block at pos0 % 256 == 0 and n_rows == 256 the tile
+// walk, the row-to-wave mapping, active/need_mask and the MFMA order are
+// v7's: the output equals flash_attention_fwd_v7 on the gathered cache bit
+// for bit.
+//
+// Garbage contract: cache rows beyond a row's position, and pages beyond the
+// walk, may hold any FINITE values without changing a bit of the output
+// (their scores are replaced by -1e30, P is exactly 0). NaN/Inf in unread V
+// rows of a walked page is outside the contract: 0 * NaN in the PV MFMA.
+// ===========================================================================
+
+struct AttnPrefillBlock { int slot, q_row0, n_rows, pos0; };
+
+// the clamps of one work row; T, B, max_pages >= 1 and max_pages * 64 fits
+// an int (the launcher checks)
+__host__ __device__ __forceinline__ AttnPrefillBlock attn_prefill_clamp(
+    int slot, int q_row0, int n_rows, int pos0, int T, int B, int max_pages) {
+  AttnPrefillBlock w;
+  int cap = T < V6_BM ? T : V6_BM;
+  if (max_pages * V6_BN < cap) cap = max_pages * V6_BN;
+  w.slot = attn_clampi(slot, 0, B - 1);
+  w.n_rows = attn_clampi(n_rows, 1, cap);
+  w.q_row0 = attn_clampi(q_row0, 0, T - w.n_rows);
+  w.pos0 = attn_clampi(pos0, 0, max_pages * V6_BN - w.n_rows);
+  return w;
+}
+
+__global__ __launch_bounds__(512) void attn_prefill_paged_kernel(
+    const u16* __restrict__ q, const u16* __restrict__ kpool,
+    const u16* __restrict__ vpool, u16* __restrict__ out,
+    const int* __restrict__ table, const int* __restrict__ work,
+    int n_heads, int gqa_group, int n_kv, int T, int B, int n_pages,
+    int max_pages, float scale2) {
+  const int wi = blockIdx.x / n_heads;
+  const int h = blockIdx.x - wi * n_heads;
+  const int hkv = h / gqa_group;
+  const int tid = threadIdx.x;
+  const int wid = tid >> 6;
+  const int lane = tid & 63;
+  const int low = lane & 31;
+  const int hi = lane >> 5;
+
+  const int* wrow = work + (long)wi * 4;
+  const AttnPrefillBlock w =
+      attn_prefill_clamp(wrow[0], wrow[1], wrow[2], wrow[3], T, B, max_pages);
+
+  __shared__ __attribute__((aligned(16))) u16 lds[ATTN_RING_U16];
+
+  // the lane's row inside the block, held at the last valid one
+  const int r0w = wid * 32;
+  const bool wave_rows = r0w < w.n_rows;
+  const int rr = r0w + low;
+  const int reff = rr < w.n_rows ? rr : w.n_rows - 1;
+  const int qrow = w.pos0 + reff;                    // cache position
+  const int q0w = w.pos0 + r0w;                      // wave's first position
+  const int qlastw = w.pos0 + (r0w + 31 < w.n_rows ? r0w + 31 : w.n_rows - 1);
+
+  AttnFrag qf[8];
+  attn_load_row(qf, q + ((long)(w.q_row0 + reff) * n_heads + h) * ATTN_D, hi);
+
+  f32x16 oacc[4];
+  attn_zero(oacc);
+  float m_run = -INFINITY, l_run = 0.f;
+
+  const int n_tiles = (w.pos0 + w.n_rows - 1) / V6_BN + 1;   // <= max_pages
+
+  // lane-constant offsets inside a page slab; wave-uniform LDS base
+  int goff[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+    goff[i] = attn_glds_page_off((tid & ~63) * 32 + i * 1024 + (tid & 63) * 16);
+  const int lslot = (tid & ~63) * 16;
+  const int* trow = table + (long)w.slot * max_pages;
+  const long slab = (long)V6_BN * ATTN_D;
+
+#define APF_PAGE(TT)                                                        \
+  attn_clampi(trow[(TT) < max_pages ? (TT) : max_pages - 1], 0, n_pages - 1)
+#define APF_ISSUE(SLOT, PAGE)                                               \
+  {                                                                         \
+    const long pb_ = ((long)(PAGE) * n_kv + hkv) * slab;                    \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                         \
+      __builtin_amdgcn_global_load_lds(                                     \
+          (const u32*)(kpool + pb_ + goff[i]),                              \
+          (u32*)&attn_ring_k(lds, SLOT)[i * 512 + lslot], 16, 0, 0);        \
+      __builtin_amdgcn_global_load_lds(                                     \
+          (const u32*)(vpool + pb_ + goff[i]),                              \
+          (u32*)&attn_ring_v(lds, SLOT)[i * 512 + lslot], 16, 0, 0);        \
+    }                                                                       \
+  }
+
+  // prologue as v7's non-causal mode: n_tiles can be 1
+  const int pg0 = APF_PAGE(0);
+  const int pg1 = APF_PAGE(1);
+  int pg_next = APF_PAGE(2);              // the entry the t = 0 issue needs
+  APF_ISSUE(0, pg0);
+  if (n_tiles > 1) APF_ISSUE(1, pg1);
+  if (n_tiles > 1) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
+  v7_barrier();
+  attn_transpose(attn_ring_v(lds, 0), attn_ring_t(lds, 0), tid);
+  v7_barrier();
+
+  for (int t = 0; t < n_tiles; ++t) {
+    const int kv0 = t * V6_BN;
+    const bool have2 = (t + 2) < n_tiles;
+    if (have2) APF_ISSUE((t + 2) % V7_RING, pg_next);
+    pg_next = APF_PAGE(t + 3);            // one tile ahead of its issue
+
+    char* kb = reinterpret_cast<char*>(attn_ring_k(lds, t % V7_RING));
+    char* vtb = attn_ring_t(lds, t & 1);
+    const bool active = wave_rows && kv0 <= qlastw;
+    const bool need_mask = kv0 + V6_BN > q0w;
+
+    f32x16 s0, s1;
+    AttnFrag pa[4];
+    float pm = -INFINITY;
+    if (active) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+#pragma unroll
+      for (int kc = 0; kc < 8; ++kc) {
+        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
+            &kb[k_byte(low, kc * 16 + hi * 8)]);
+        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kc].v, s0, 0, 0, 0);
+        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
+            &kb[k_byte(32 + low, kc * 16 + hi * 8)]);
+        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kc].v, s1, 0, 0, 0);
+      }
+      if (need_mask) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          float x0 = s0[r] * scale2;
+          if (kvr > qrow) x0 = -1e30f;
+          s0[r] = x0;
+          float x1 = s1[r] * scale2;
+          if (kvr + 32 > qrow) x1 = -1e30f;
+          s1[r] = x1;
+          pm = fmaxf(pm, fmaxf(x0, x1));
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          s0[r] *= scale2;
+          s1[r] *= scale2;
+          pm = fmaxf(pm, fmaxf(s0[r], s1[r]));
+        }
+      }
+      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
+
+      if (!__all(pm - m_run <= 8.0f)) {
+        const float mn = fmaxf(m_run, pm);
+        const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
+        m_run = mn;
+        l_run *= alpha;
+#pragma unroll
+        for (int ds = 0; ds < 4; ++ds)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;
+      }
+      float psum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p0 = exp2_raw(s0[r] - m_run);
+        const float p1 = exp2_raw(s1[r] - m_run);
+        s0[r] = p0;
+        s1[r] = p1;
+        psum += p0 + p1;
+      }
+      psum += __shfl_xor(psum, 32, 64);
+      l_run += psum;
+
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+          pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);
+        }
+      }
+
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int ds = 0; ds < 4; ++ds) {
+          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
+              &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
+          oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              vf, pa[c].v, oacc[ds], 0, 0, 0);
+        }
+      }
+    }
+    if (t + 1 < n_tiles) {
+      if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
+      attn_transpose(attn_ring_v(lds, (t + 1) % V7_RING),
+                     attn_ring_t(lds, (t + 1) & 1), tid);
+    }
+    v7_barrier();
+  }
+#undef APF_ISSUE
+#undef APF_PAGE
+
+  if (rr < w.n_rows) {
+    const float inv_l = 1.0f / l_run;
+    u16* orow = out + ((long)(w.q_row0 + rr) * n_heads + h) * ATTN_D;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int d0 = 8 * g + 4 * hi + 32 * ds;
+        uint2 wv;
+        wv.x = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
+                           oacc[ds][4 * g + 1] * inv_l);
+        wv.y = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
+                           oacc[ds][4 * g + 3] * inv_l);
+        *reinterpret_cast<uint2*>(orow + d0) = wv;
+      }
+    }
+  }
 }
 
 // ===========================================================================
@@ -2628,6 +2887,46 @@ extern "C" int attn_fwd_v5(void* stream, const void* q, const void* k,
                      (const u16*)q, (const u16*)k, (const u16*)v, (u16*)out,
                      (float*)lse, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss,
                      v_sb, v_sh, v_ss, n_heads, S, scale);
+  return 0;
+}
+
+// paged prefill forward (attn_prefill_paged_kernel): q/out [T, H, 128] bf16
+// packed rows, pools [n_pages, n_kv, 64, 128] bf16 contiguous, block_table
+// [B, max_pages] int32, work [n_blocks, 4] int32 device rows (slot, q_row0,
+// n_rows, pos0), heaviest blocks first.
+extern "C" int attn_prefill_paged(void* stream, const void* q,
+                                  const void* k_pool, const void* v_pool,
+                                  void* out, const void* block_table,
+                                  const void* work, int n_blocks, int T,
+                                  int n_heads, int n_kv_heads, int B,
+                                  int n_pages, int max_pages, float scale) {
+  if (n_blocks <= 0 || T <= 0 || n_heads <= 0 || n_kv_heads <= 0 ||
+      n_heads % n_kv_heads != 0 || B <= 0 || n_pages <= 0 ||
+      max_pages <= 0 || max_pages > (1 << 24) || !block_table || !work ||
+      (long)n_blocks * n_heads > 0x7fffffffL)
+    return -1;
+  dim3 grid((unsigned)(n_blocks * n_heads)), block(512);
+  hipLaunchKernelGGL(attn_prefill_paged_kernel, grid, block, 0,
+                     reinterpret_cast<hipStream_t>(stream), (const u16*)q,
+                     (const u16*)k_pool, (const u16*)v_pool, (u16*)out,
+                     (const int*)block_table, (const int*)work, n_heads,
+                     n_heads / n_kv_heads, n_kv_heads, T, B, n_pages,
+                     max_pages, scale * ATTN_LOG2E);
+  return 0;
+}
+
+// Host-callable clamp of one work row (tests/test_paged_prefill_cpu.py):
+// io = (slot, q_row0, n_rows, pos0) in, the values the kernel uses out.
+extern "C" int attn_prefill_work_decode(int* io, int T, int B,
+                                        int max_pages) {
+  if (!io || T <= 0 || B <= 0 || max_pages <= 0 || max_pages > (1 << 24))
+    return -1;
+  const AttnPrefillBlock w =
+      attn_prefill_clamp(io[0], io[1], io[2], io[3], T, B, max_pages);
+  io[0] = w.slot;
+  io[1] = w.q_row0;
+  io[2] = w.n_rows;
+  io[3] = w.pos0;
   return 0;
 }
 

@@ -1454,6 +1454,60 @@ __global__ void rope_cache_paged_kernel(
   dst[d + half] = f2bf(x1 * sn + x2 * c);
 }
 
+// rope_cache_paged_kernel for T packed tokens of several sequences (paged
+// prefill): token t belongs to slot tok_slot[t] and sits at cache position
+// tok_pos[t]. Same angle expression, so a row written here is the row the
+// decode kernel would have written. A token with tok_pos < 0 writes no k/v
+// and zeros its q rows. The slot is clamped into [0, B) next to the
+// position and page clamps: any tok_slot/tok_pos/table content is
+// memory-safe.
+__global__ void rope_cache_paged_rows_kernel(
+    const u16* __restrict__ qkv, u16* __restrict__ qout,
+    u16* __restrict__ kpool, u16* __restrict__ vpool,
+    const float* __restrict__ inv_freq, const int* __restrict__ table,
+    const int* __restrict__ tok_slot, const long* __restrict__ tok_pos,
+    int B, int nh, int nkv, int n_pages, int max_pages, int D) {
+  const int t = blockIdx.x;
+  const int hx = blockIdx.y;             // 0..nh-1 q, ..+nkv k, ..+nkv v
+  const int d = threadIdx.x;             // 0 .. D/2-1
+  const int half = D / 2;
+  long pos = tok_pos[t];
+  if (pos < 0) {
+    if (hx < nh) {
+      u16* z = qout + ((long)t * nh + hx) * D;
+      z[d] = 0;
+      z[d + half] = 0;
+    }
+    return;
+  }
+  pos = apg_clamp_pos(pos, max_pages);
+  int b = tok_slot[t];
+  b = b < 0 ? 0 : (b >= B ? B - 1 : b);
+  const u16* src = qkv + ((long)t * (nh + 2 * nkv)) * D + (long)hx * D;
+  const float x1 = bf2f(src[d]), x2 = bf2f(src[d + half]);
+  u16* dst;
+  if (hx < nh) {
+    dst = qout + ((long)t * nh + hx) * D;
+  } else {
+    const int page = apg_phys_page(table, b, max_pages,
+                                   (int)(pos / APG_ROWS), n_pages);
+    const int r = (int)(pos % APG_ROWS);
+    if (hx < nh + nkv) {
+      dst = kpool + ((((long)page * nkv + (hx - nh)) * APG_ROWS) + r) * D;
+    } else {
+      u16* vd = vpool
+          + ((((long)page * nkv + (hx - nh - nkv)) * APG_ROWS) + r) * D;
+      vd[d] = src[d];
+      vd[d + half] = src[d + half];
+      return;
+    }
+  }
+  float c, sn;
+  __sincosf((float)pos * inv_freq[d], &sn, &c);
+  dst[d] = f2bf(x1 * c - x2 * sn);
+  dst[d + half] = f2bf(x1 * sn + x2 * c);
+}
+
 
 // ---------------------------------------------------------------------------
 // Decode GEMV + SwiGLU: y[n][m] = silu(x @ Wg[m]) * (x @ Wu[m]) where the
@@ -2134,6 +2188,28 @@ int rope_cache_paged(void* stream, const void* qkv, void* qout,
                      (u16*)v_pool, (const float*)inv_freq,
                      (const int*)block_table, (const long*)pos_dev, nh,
                      nkv, n_pages, max_pages, D);
+  return 0;
+}
+
+// paged prefill rope + cache write (rope_cache_paged_rows_kernel): qkv
+// packed [T, (nh+2*nkv)*D] bf16, qout [T, nh, D], tok_slot [T] int32,
+// tok_pos [T] long (negative = padding token), block_table [B, max_pages].
+int rope_cache_paged_rows(void* stream, const void* qkv, void* qout,
+                          void* k_pool, void* v_pool, const void* inv_freq,
+                          const void* block_table, const void* tok_slot,
+                          const void* tok_pos, int T, int B, int nh, int nkv,
+                          int n_pages, int max_pages, int D) {
+  if (D <= 0 || D % 16 != 0 || D / 2 > 1024 || nh <= 0 || nkv <= 0 ||
+      nh + 2 * nkv > 65535 || T <= 0 || B <= 0 || n_pages <= 0 ||
+      max_pages <= 0 || !block_table || !tok_slot || !tok_pos)
+    return -1;
+  dim3 grid((unsigned)T, (unsigned)(nh + 2 * nkv)), block(D / 2);
+  hipLaunchKernelGGL(rope_cache_paged_rows_kernel, grid, block, 0, STREAM,
+                     (const u16*)qkv, (u16*)qout, (u16*)k_pool,
+                     (u16*)v_pool, (const float*)inv_freq,
+                     (const int*)block_table, (const int*)tok_slot,
+                     (const long*)tok_pos, B, nh, nkv, n_pages, max_pages,
+                     D);
   return 0;
 }
 

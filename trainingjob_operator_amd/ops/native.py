@@ -85,6 +85,18 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # n_pages, max_pages, D)
     _sig(lib.rope_cache_paged, [vp, vp, vp, vp, vp, vp, vp, vp,
                                 i, i, i, i, i, i], i)
+    # paged prefill: (qkv, qout, k_pool, v_pool, inv_freq, block_table,
+    # tok_slot int32 [T], tok_pos int64 [T], T, B, nh, nkv, n_pages,
+    # max_pages, D)
+    _sig(lib.rope_cache_paged_rows, [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     i, i, i, i, i, i, i], i)
+    # (q [T,H,128], k_pool, v_pool, out, block_table, work int32 [n, 4],
+    # n_blocks, T, H, n_kv, B, n_pages, max_pages, scale)
+    _sig(lib.attn_prefill_paged, [vp, vp, vp, vp, vp, vp, vp,
+                                  i, i, i, i, i, i, i, f], i)
+    # clamp of one work row (host callable): (io int[4], T, B, max_pages)
+    _sig(lib.attn_prefill_work_decode, [ctypes.POINTER(ctypes.c_int),
+                                        i, i, i], i)
     _sig(lib.swiglu_fwd, [vp, vp, vp, vp, l], i)
     _sig(lib.swiglu_bwd, [vp, vp, vp, vp, vp, vp, l], i)
     _sig(lib.swiglu_packed_fwd, [vp, vp, vp, l, i], i)

@@ -150,6 +150,75 @@ def rope_cache_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
     return qr.contiguous()
 
 
+def rope_cache_paged_rows(qkv: torch.Tensor, k_pool: torch.Tensor,
+                          v_pool: torch.Tensor, inv_freq: torch.Tensor,
+                          block_table: torch.Tensor, tok_slot: torch.Tensor,
+                          tok_pos: torch.Tensor, num_heads: int,
+                          num_kv_heads: int) -> torch.Tensor:
+    """Twin of rope_cache_paged_rows: rope_cache_paged for T packed tokens
+    of several sequences. Token t belongs to block-table row tok_slot[t]
+    (clamped into the table) and sits at cache position tok_pos[t]; a
+    token with tok_pos < 0 writes nothing and gets a zero q. Every token is
+    its own 'slot' of the per-sequence twin, with its sequence's table
+    row, so the result equals that twin called token by token."""
+    B = block_table.shape[0]
+    slot = tok_slot.to(block_table.device).long().clamp(0, B - 1)
+    return rope_cache_paged(qkv, k_pool, v_pool, inv_freq,
+                            block_table[slot], tok_pos, num_heads,
+                            num_kv_heads)
+
+
+PREFILL_BLOCK_ROWS = 256    # q rows of one work-list block (the v7 tile)
+
+
+def prefill_work_clamp(row, T: int, B: int, max_pages: int):
+    """(slot, q_row0, n_rows, pos0) as the prefill kernel uses them: every
+    field clamped so that all rows and positions stay inside q and the
+    table, whatever the row holds."""
+    slot, q_row0, n_rows, pos0 = (int(x) for x in row)
+    cap = min(PREFILL_BLOCK_ROWS, T, max_pages * PAGE_ROWS)
+    slot = min(max(slot, 0), B - 1)
+    n_rows = min(max(n_rows, 1), cap)
+    q_row0 = min(max(q_row0, 0), T - n_rows)
+    pos0 = min(max(pos0, 0), max_pages * PAGE_ROWS - n_rows)
+    return slot, q_row0, n_rows, pos0
+
+
+def prefill_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                            v_pool: torch.Tensor, block_table: torch.Tensor,
+                            work: torch.Tensor, scale: float,
+                            out: Optional[torch.Tensor] = None
+                            ) -> torch.Tensor:
+    """Twin of attn_prefill_paged: q [T, H, D] packed rows of several
+    sequences. work [n, 4] int32 rows (slot, q_row0, n_rows, pos0): rows
+    q_row0 .. q_row0+n_rows-1 sit at cache positions pos0 .. of block-table
+    row `slot`, and the row at position p attends cache rows 0..p. fp32
+    math, any head_dim, result in q.dtype. Rows of `out` (zeros if not
+    given) that no work row names are left as they are; cache rows beyond
+    a row's position are never used, whatever they hold."""
+    T, H, D = q.shape
+    n_pages, n_kv, R, _ = k_pool.shape
+    G = H // n_kv
+    B, max_pages = block_table.shape
+    o = torch.zeros_like(q) if out is None else out
+    tbl = block_table.long().clamp(0, n_pages - 1).cpu()
+    for row in work.cpu().tolist():
+        slot, q_row0, n_rows, pos0 = prefill_work_clamp(row, T, B, max_pages)
+        L = pos0 + n_rows
+        pages = tbl[slot, :(L + R - 1) // R].to(k_pool.device)
+        k = k_pool[pages].permute(1, 0, 2, 3).reshape(n_kv, -1, D)[:, :L]
+        v = v_pool[pages].permute(1, 0, 2, 3).reshape(n_kv, -1, D)[:, :L]
+        qb = q[q_row0:q_row0 + n_rows].float().reshape(n_rows, n_kv, G, D)
+        s = torch.einsum("rkgd,ksd->kgrs", qb, k.float()) * scale
+        p_row = pos0 + torch.arange(n_rows, device=q.device)
+        seen = torch.arange(L, device=q.device)[None, :] <= p_row[:, None]
+        s = s.masked_fill(~seen[None, None], float("-inf"))
+        p = torch.softmax(s, dim=-1)
+        ob = torch.einsum("kgrs,ksd->rkgd", p, v.float())
+        o[q_row0:q_row0 + n_rows] = ob.reshape(n_rows, H, D).to(o.dtype)
+    return o
+
+
 def swiglu_fwd(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     gf = g.float()
     return (gf * torch.sigmoid(gf) * u.float()).to(g.dtype)
