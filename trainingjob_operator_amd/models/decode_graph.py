@@ -29,7 +29,7 @@ from __future__ import annotations
 import torch
 
 from ..ops import decode_attention, decode_linear, fused_rmsnorm, native
-from .generate import KVCache, _mlp_cached
+from .generate import KVCache, _layers_cached
 from .llama import LlamaModel
 
 
@@ -41,14 +41,10 @@ def _step_static(model: LlamaModel, cur: torch.Tensor, cache: KVCache,
     import math
     cfg = model.cfg
     B = cur.shape[0]
-    x = model.embed(cur)                                   # [B, 1, H]
     mask = None          # built lazily: only the einsum fallback needs it
-    residual = None
-    for li, blk in enumerate(model.blocks):
-        attn = blk.attn
-        normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
-                                         residual, cfg.norm_eps)
-        qkv = decode_linear(normed, attn.qkv_proj.weight)
+
+    def attend(li, blk, qkv):
+        nonlocal mask
         # one fused launch: rope q -> contiguous buffer, rope k ->
         # cache[pos], copy v -> cache[pos] (vs 2 rope + 2 index_copy)
         lib = native.load(require=True)
@@ -77,16 +73,9 @@ def _step_static(model: LlamaModel, cur: torch.Tensor, cache: KVCache,
             scores = scores * scale + mask
             p = torch.softmax(scores, dim=-1)
             o = torch.einsum("bkgs,bksd->bkgd", p, vv.float())
-        o = o.reshape(B, 1, cfg.num_heads * cfg.head_dim).to(x.dtype)
-        attn_out = decode_linear(o, attn.o_proj.weight)
-        normed, residual = fused_rmsnorm(attn_out,
-                                         blk.post_attn_norm_weight,
-                                         residual, cfg.norm_eps)
-        # MoE blocks are capturable because the routed decode path keeps
-        # routing on device (parallel/ep.py _decode_forward): topk ->
-        # pointer-table GEMVs, fixed shapes, no host syncs
-        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
-            else blk.moe(normed)
+        return o
+
+    x, residual = _layers_cached(model, model.embed(cur), attend)  # [B, 1, H]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
     logits = decode_linear(normed, model.lm_head.weight)

@@ -180,6 +180,35 @@ def _mlp_cached(mlp, x: torch.Tensor) -> torch.Tensor:
     return decode_linear(h, mlp.down_proj.weight)
 
 
+def _layers_cached(model, x: torch.Tensor, attend):
+    """The blocks of a cached step whose attention works on the packed qkv
+    projection (decode_graph._step_static, paged._step_paged,
+    paged._prefill_paged): per block input norm -> qkv GEMV ->
+    attend(li, blk, qkv), the attention output before o_proj (any shape
+    with x's rows) -> o_proj -> post-attention norm -> mlp/moe. x is
+    [B, S, H]; returns (x, residual) for the caller's final norm."""
+    cfg = model.cfg
+    B, S, _ = x.shape
+    residual = None
+    for li, blk in enumerate(model.blocks):
+        normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
+                                         residual, cfg.norm_eps)
+        qkv = decode_linear(normed, blk.attn.qkv_proj.weight)
+        o = attend(li, blk, qkv)
+        o = o.reshape(B, S, cfg.num_heads * cfg.head_dim).to(x.dtype)
+        attn_out = decode_linear(o, blk.attn.o_proj.weight)
+        normed, residual = fused_rmsnorm(attn_out,
+                                         blk.post_attn_norm_weight,
+                                         residual, cfg.norm_eps)
+        # dense blocks carry .mlp; MoE blocks carry .moe. The routed decode
+        # path keeps routing on device (parallel/ep.py _decode_forward:
+        # topk -> pointer-table GEMVs, fixed shapes, no host syncs), so MoE
+        # blocks are stream-capturable too
+        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
+            else blk.moe(normed)
+    return x, residual
+
+
 @torch.no_grad()
 def _forward_cached(model: LlamaModel, tokens: torch.Tensor,
                     cache: KVCache) -> torch.Tensor:

@@ -42,7 +42,7 @@ import torch
 from ..ops import (decode_attention_paged, decode_linear, fused_rmsnorm,
                    prefill_attention_paged, prefill_work, reference,
                    rope_cache_paged, rope_cache_paged_rows)
-from .generate import KVCache, _forward_cached, _mlp_cached, _sample
+from .generate import KVCache, _forward_cached, _layers_cached, _sample
 
 PAGE_ROWS = reference.PAGE_ROWS
 
@@ -231,13 +231,8 @@ def _step_paged(model, cur: torch.Tensor,
     cfg = model.cfg
     B = cur.shape[0]
     scale = 1.0 / math.sqrt(cfg.head_dim)
-    x = model.embed(cur)                                   # [B, 1, H]
-    residual = None
-    for li, blk in enumerate(model.blocks):
-        attn = blk.attn
-        normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
-                                         residual, cfg.norm_eps)
-        qkv = decode_linear(normed, attn.qkv_proj.weight)
+
+    def attend(li, blk, qkv):
         q = rope_cache_paged(qkv.reshape(B, -1), cache.k[li], cache.v[li],
                              model.inv_freq, cache.block_table, cache.pos,
                              cfg.num_heads, cfg.num_kv_heads)
@@ -248,13 +243,9 @@ def _step_paged(model, cur: torch.Tensor,
             o = reference.decode_attention_paged(
                 q, cache.k[li], cache.v[li], cache.block_table, cache.pos,
                 scale)
-        o = o.reshape(B, 1, cfg.num_heads * cfg.head_dim).to(x.dtype)
-        attn_out = decode_linear(o, attn.o_proj.weight)
-        normed, residual = fused_rmsnorm(attn_out,
-                                         blk.post_attn_norm_weight,
-                                         residual, cfg.norm_eps)
-        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
-            else blk.moe(normed)
+        return o
+
+    x, residual = _layers_cached(model, model.embed(cur), attend)  # [B, 1, H]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
     logits = decode_linear(normed, model.lm_head.weight)
@@ -282,13 +273,8 @@ def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
     scale = 1.0 / math.sqrt(cfg.head_dim)
     work, tok_slot, tok_pos = prefill_work(chunks, dev)
     assert tok_slot.numel() == T, (tok_slot.numel(), T)
-    x = model.embed(tokens)                                # [1, T, H]
-    residual = None
-    for li, blk in enumerate(model.blocks):
-        attn = blk.attn
-        normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
-                                         residual, cfg.norm_eps)
-        qkv = decode_linear(normed, attn.qkv_proj.weight)
+
+    def attend(li, blk, qkv):
         q = rope_cache_paged_rows(qkv.reshape(T, -1), cache.k[li],
                                   cache.v[li], model.inv_freq,
                                   cache.block_table, tok_slot, tok_pos,
@@ -298,13 +284,10 @@ def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
         if o is None:                 # off-GPU or head_dim != 128: twin
             o = reference.prefill_attention_paged(
                 q, cache.k[li], cache.v[li], cache.block_table, work, scale)
-        o = o.reshape(1, T, cfg.num_heads * cfg.head_dim).to(x.dtype)
-        attn_out = decode_linear(o, attn.o_proj.weight)
-        normed, residual = fused_rmsnorm(attn_out,
-                                         blk.post_attn_norm_weight,
-                                         residual, cfg.norm_eps)
-        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
-            else blk.moe(normed)
+        return o
+
+    x, residual = _layers_cached(model, model.embed(tokens),   # [1, T, H]
+                                 attend)
     if not last_rows:                 # no prompt ends in this batch
         return x.new_zeros(0, model.lm_head.weight.shape[0])
     rows = torch.tensor(list(last_rows), dtype=torch.long, device=dev)

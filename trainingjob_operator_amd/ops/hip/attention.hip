@@ -1034,6 +1034,116 @@ __device__ __forceinline__ void attn_wave_minmax(int x, int& lo, int& hi_) {
   hi_ = __builtin_amdgcn_readfirstlane(mx);
 }
 
+// One kv tile of the v7 forward for one wave: S = K Q^T (2 x 32x32 MFMA
+// accumulators), scale and mask, online softmax with the lazy (> 8) rescale,
+// P repacked to bf16, O += V^T P. One text for attn_fwd_v7_kernel<MASK> and
+// attn_prefill_paged_kernel; a macro, not a function, because passing qf,
+// oacc, m_run and l_run by reference moved every caller's stream
+// (profiles/r14_paged_fold.md). It reads the names in scope where it is
+// used: kb, vtb (this tile's K rows and transposed V), kv0, active,
+// need_mask, qf, qrow, low, hi, scale2, DOC, start, and updates oacc, m_run,
+// l_run. Without documents DOC is false and start 0. Documents (see the v7
+// header): a row whose tiles so far were all masked sits at m_run = -1e30
+// and is rescaled by exactly 0 at its first real one.
+#define ATTN_V7_TILE()                                                      \
+  f32x16 s0, s1;                                                            \
+  AttnFrag pa[4];                                                           \
+  float pm = -INFINITY;                                                     \
+  if (active) {                                                             \
+    _Pragma("unroll")                                                       \
+    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }              \
+    _Pragma("unroll")                                                       \
+    for (int kc = 0; kc < 8; ++kc) {                                        \
+      bf16x8 a0 = *reinterpret_cast<const bf16x8*>(                         \
+          &kb[k_byte(low, kc * 16 + hi * 8)]);                              \
+      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                         \
+          a0, qf[kc].v, s0, 0, 0, 0);                                       \
+      bf16x8 a1 = *reinterpret_cast<const bf16x8*>(                         \
+          &kb[k_byte(32 + low, kc * 16 + hi * 8)]);                         \
+      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                         \
+          a1, qf[kc].v, s1, 0, 0, 0);                                       \
+    }                                                                       \
+    if (need_mask) {                                                        \
+      _Pragma("unroll")                                                     \
+      for (int r = 0; r < 16; ++r) {                                        \
+        const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;              \
+        float x0 = s0[r] * scale2;                                          \
+        if (kvr > qrow || (DOC && kvr < start)) x0 = -1e30f;                \
+        s0[r] = x0;                                                         \
+        float x1 = s1[r] * scale2;                                          \
+        if (kvr + 32 > qrow || (DOC && kvr + 32 < start)) x1 = -1e30f;      \
+        s1[r] = x1;                                                         \
+        pm = fmaxf(pm, fmaxf(x0, x1));                                      \
+      }                                                                     \
+    } else {                                                                \
+      _Pragma("unroll")                                                     \
+      for (int r = 0; r < 16; ++r) {                                        \
+        s0[r] *= scale2;                                                    \
+        s1[r] *= scale2;                                                    \
+        pm = fmaxf(pm, fmaxf(s0[r], s1[r]));                                \
+      }                                                                     \
+    }                                                                       \
+    pm = fmaxf(pm, __shfl_xor(pm, 32, 64));                                 \
+    if (!__all(pm - m_run <= 8.0f)) {                                       \
+      const float mn = fmaxf(m_run, pm);                                    \
+      const float alpha = (m_run == -INFINITY)                              \
+          ? 0.f : exp2_raw(m_run - mn);                                     \
+      m_run = mn;                                                           \
+      l_run *= alpha;                                                       \
+      _Pragma("unroll")                                                     \
+      for (int ds = 0; ds < 4; ++ds)                                        \
+        _Pragma("unroll")                                                   \
+        for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;                  \
+    }                                                                       \
+    float psum = 0.f;                                                       \
+    _Pragma("unroll")                                                       \
+    for (int r = 0; r < 16; ++r) {                                          \
+      const float p0 = exp2_raw(s0[r] - m_run);                             \
+      const float p1 = exp2_raw(s1[r] - m_run);                             \
+      s0[r] = p0;                                                           \
+      s1[r] = p1;                                                           \
+      psum += p0 + p1;                                                      \
+    }                                                                       \
+    psum += __shfl_xor(psum, 32, 64);                                       \
+    l_run += psum;                                                          \
+    _Pragma("unroll")                                                       \
+    for (int sub = 0; sub < 2; ++sub) {                                     \
+      _Pragma("unroll")                                                     \
+      for (int cc = 0; cc < 2; ++cc) {                                      \
+        pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);       \
+      }                                                                     \
+    }                                                                       \
+    _Pragma("unroll")                                                       \
+    for (int c = 0; c < 4; ++c) {                                           \
+      _Pragma("unroll")                                                     \
+      for (int ds = 0; ds < 4; ++ds) {                                      \
+        bf16x8 vf = *reinterpret_cast<const bf16x8*>(                       \
+            &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);                 \
+        oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                 \
+            vf, pa[c].v, oacc[ds], 0, 0, 0);                                \
+      }                                                                     \
+    }                                                                       \
+  }
+
+// the lane's share of one output row, O / l as bf16: 4 d per uint2 store
+__device__ __forceinline__ void attn_v7_store_row(const f32x16 (&oacc)[4],
+                                                  float inv_l, u16* orow,
+                                                  int hi) {
+#pragma unroll
+  for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d0 = 8 * g + 4 * hi + 32 * ds;
+      uint2 wv;
+      wv.x = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
+                         oacc[ds][4 * g + 1] * inv_l);
+      wv.y = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
+                         oacc[ds][4 * g + 3] * inv_l);
+      *reinterpret_cast<uint2*>(orow + d0) = wv;
+    }
+  }
+}
+
 template <int MASK>
 __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -1123,87 +1233,7 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     const bool need_mask =
         CAUSAL && (kv0 + V6_BN > q0w || (DOC && kv0 < smax));
 
-    f32x16 s0, s1;
-    AttnFrag pa[4];
-    float pm = -INFINITY;
-    if (active) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-#pragma unroll
-      for (int kc = 0; kc < 8; ++kc) {
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(low, kc * 16 + hi * 8)]);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kc].v, s0, 0, 0, 0);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(32 + low, kc * 16 + hi * 8)]);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kc].v, s1, 0, 0, 0);
-      }
-      if (need_mask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          float x0 = s0[r] * scale2;
-          if (kvr > qrow || (DOC && kvr < start)) x0 = -1e30f;
-          s0[r] = x0;
-          float x1 = s1[r] * scale2;
-          if (kvr + 32 > qrow || (DOC && kvr + 32 < start)) x1 = -1e30f;
-          s1[r] = x1;
-          pm = fmaxf(pm, fmaxf(x0, x1));
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] *= scale2;
-          s1[r] *= scale2;
-          pm = fmaxf(pm, fmaxf(s0[r], s1[r]));
-        }
-      }
-      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
-
-      // documents (see the header): a row whose tiles so far were all masked
-      // sits at m_run = -1e30 and is rescaled by exactly 0 here at its first
-      // real one
-      if (!__all(pm - m_run <= 8.0f)) {
-        const float mn = fmaxf(m_run, pm);
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
-        m_run = mn;
-        l_run *= alpha;
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;
-      }
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p0 = exp2_raw(s0[r] - m_run);
-        const float p1 = exp2_raw(s1[r] - m_run);
-        s0[r] = p0;
-        s1[r] = p1;
-        psum += p0 + p1;
-      }
-      psum += __shfl_xor(psum, 32, 64);
-      l_run += psum;
-
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);
-        }
-      }
-
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) {
-          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-              &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-          oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              vf, pa[c].v, oacc[ds], 0, 0, 0);
-        }
-      }
-    }
+    ATTN_V7_TILE()
     // end-of-tile: wait slot t+1 (counted — t+2 stays in flight), build
     // the NEXT transposed image (different Vt buffer than this tile's PV
     // reads, so it needs no pre-barrier), then ONE raw barrier guarding
@@ -1216,23 +1246,9 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
     v7_barrier();
   }
 
-  const float inv_l = 1.0f / l_run;
-  u16* orow = out + (long)b * o_sb + (long)h * o_sh + (long)qrow * o_ss;
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 8 * g + 4 * hi + 32 * ds;
-      const unsigned w0 = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
-                                      oacc[ds][4 * g + 1] * inv_l);
-      const unsigned w1 = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
-                                      oacc[ds][4 * g + 3] * inv_l);
-      uint2 wv;
-      wv.x = w0;
-      wv.y = w1;
-      *reinterpret_cast<uint2*>(orow + d0) = wv;
-    }
-  }
+  attn_v7_store_row(
+      oacc, 1.0f / l_run,
+      out + (long)b * o_sb + (long)h * o_sh + (long)qrow * o_ss, hi);
   if (hi == 0)
     lse[((long)b * n_heads + h) * S + qrow] =
         m_run * 0.6931471805599453f + __logf(l_run);
@@ -1242,8 +1258,8 @@ __global__ __launch_bounds__(512) void attn_fwd_v7_kernel(
 // Paged prefill forward: the causal v7 forward with queries at arbitrary
 // cache positions and K/V tiles found through a block table. A sibling of
 // attn_fwd_v7_kernel built from the same pieces (attn_load_row, the ring,
-// attn_transpose, the S/softmax/PV body, statement for statement), so the v7
-// instantiations keep their instruction streams.
+// attn_transpose, ATTN_V7_TILE); its block source, ring issue, active /
+// need_mask and epilogue guard are its own.
 //
 // q and out are packed rows [T, H, 128]; the pools are [n_pages, n_kv, 64,
 // 128], table [B, max_pages] int32 as in the paged decode kernels. A cache
@@ -1327,6 +1343,8 @@ __global__ __launch_bounds__(512) void attn_prefill_paged_kernel(
   const int qrow = w.pos0 + reff;                    // cache position
   const int q0w = w.pos0 + r0w;                      // wave's first position
   const int qlastw = w.pos0 + (r0w + 31 < w.n_rows ? r0w + 31 : w.n_rows - 1);
+  constexpr bool DOC = false;                        // ATTN_V7_TILE: causal
+  const int start = 0;
 
   AttnFrag qf[8];
   attn_load_row(qf, q + ((long)(w.q_row0 + reff) * n_heads + h) * ATTN_D, hi);
@@ -1383,84 +1401,7 @@ __global__ __launch_bounds__(512) void attn_prefill_paged_kernel(
     const bool active = wave_rows && kv0 <= qlastw;
     const bool need_mask = kv0 + V6_BN > q0w;
 
-    f32x16 s0, s1;
-    AttnFrag pa[4];
-    float pm = -INFINITY;
-    if (active) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-#pragma unroll
-      for (int kc = 0; kc < 8; ++kc) {
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(low, kc * 16 + hi * 8)]);
-        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, qf[kc].v, s0, 0, 0, 0);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
-            &kb[k_byte(32 + low, kc * 16 + hi * 8)]);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, qf[kc].v, s1, 0, 0, 0);
-      }
-      if (need_mask) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          float x0 = s0[r] * scale2;
-          if (kvr > qrow) x0 = -1e30f;
-          s0[r] = x0;
-          float x1 = s1[r] * scale2;
-          if (kvr + 32 > qrow) x1 = -1e30f;
-          s1[r] = x1;
-          pm = fmaxf(pm, fmaxf(x0, x1));
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] *= scale2;
-          s1[r] *= scale2;
-          pm = fmaxf(pm, fmaxf(s0[r], s1[r]));
-        }
-      }
-      pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
-
-      if (!__all(pm - m_run <= 8.0f)) {
-        const float mn = fmaxf(m_run, pm);
-        const float alpha = (m_run == -INFINITY) ? 0.f : exp2_raw(m_run - mn);
-        m_run = mn;
-        l_run *= alpha;
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) oacc[ds][r] *= alpha;
-      }
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p0 = exp2_raw(s0[r] - m_run);
-        const float p1 = exp2_raw(s1[r] - m_run);
-        s0[r] = p0;
-        s1[r] = p1;
-        psum += p0 + p1;
-      }
-      psum += __shfl_xor(psum, 32, 64);
-      l_run += psum;
-
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);
-        }
-      }
-
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int ds = 0; ds < 4; ++ds) {
-          bf16x8 vf = *reinterpret_cast<const bf16x8*>(
-              &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
-          oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              vf, pa[c].v, oacc[ds], 0, 0, 0);
-        }
-      }
-    }
+    ATTN_V7_TILE()
     if (t + 1 < n_tiles) {
       if (have2) v7_wait_vmcnt4(); else v7_wait_vmcnt0();
       attn_transpose(attn_ring_v(lds, (t + 1) % V7_RING),
@@ -1471,23 +1412,10 @@ __global__ __launch_bounds__(512) void attn_prefill_paged_kernel(
 #undef APF_ISSUE
 #undef APF_PAGE
 
-  if (rr < w.n_rows) {
-    const float inv_l = 1.0f / l_run;
-    u16* orow = out + ((long)(w.q_row0 + rr) * n_heads + h) * ATTN_D;
-#pragma unroll
-    for (int ds = 0; ds < 4; ++ds) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = 8 * g + 4 * hi + 32 * ds;
-        uint2 wv;
-        wv.x = cvt_pk_bf16(oacc[ds][4 * g + 0] * inv_l,
-                           oacc[ds][4 * g + 1] * inv_l);
-        wv.y = cvt_pk_bf16(oacc[ds][4 * g + 2] * inv_l,
-                           oacc[ds][4 * g + 3] * inv_l);
-        *reinterpret_cast<uint2*>(orow + d0) = wv;
-      }
-    }
-  }
+  if (rr < w.n_rows)
+    attn_v7_store_row(
+        oacc, 1.0f / l_run,
+        out + ((long)(w.q_row0 + rr) * n_heads + h) * ATTN_D, hi);
 }
 
 // ===========================================================================
@@ -1709,6 +1637,46 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
 #define BV_DOT_U16 (ATTN_D * (VT_PITCH_B / 2) + 128)
 #define BV_LSE_U16 128                      // 64 f32
 #define BV_BUF_U16 (BV_Q_U16 + BV_DOT_U16 + BV_LSE_U16)
+
+// Staging of one q tile for the dV walks (attn_bwd_dv_kernel and
+// attn_bwd_dv_pair_kernel): Q rows by glds, the two dO rows of the lane into
+// dtst, the lse tile; then dtst into the transposed dO image. Macros over the
+// names in scope (lds, qgp, dtp, dtst, qstep, dostep, lbase, wu64, tid,
+// LSEOFF, DOTOFF): as shared functions they moved the stream of all four
+// dv/dk kernels (profiles/r09_attention_refactor.md).
+#define BV_STAGE_IN(BUFI, QT)                                               \
+    {                                                                       \
+      _Pragma("unroll")                                                     \
+      for (int i = 0; i < 2; ++i) {                                         \
+        __builtin_amdgcn_global_load_lds(                                   \
+            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
+            16, 0, 0);                                                      \
+        qgp[i] += qstep;                                                    \
+      }                                                                     \
+      dtst[0] = *reinterpret_cast<const uint4*>(dtp[0]);                    \
+      dtst[1] = *reinterpret_cast<const uint4*>(dtp[1]);                    \
+      dtp[0] += dostep;                                                     \
+      dtp[1] += dostep;                                                     \
+      if (tid < 64)                                                         \
+        *reinterpret_cast<float*>(                                          \
+            &lds[BUFI][LSEOFF / 2 + tid * 2]) =                             \
+            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
+    }
+#define BV_WRITE_DOT(BUF)                                                   \
+    {                                                                       \
+      const int rp2_ = (tid >> 4) * 2;                                      \
+      const int c8_ = (tid & 15) * 8;                                       \
+      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
+      va_.u4 = dtst[0];                                                     \
+      vb_.u4 = dtst[1];                                                     \
+      _Pragma("unroll")                                                     \
+      for (int j = 0; j < 8; ++j) {                                         \
+        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
+        *reinterpret_cast<u32*>(&(BUF)[DOTOFF + vt_byte(c8_ + j, rp2_)]) =  \
+            pair_;                                                          \
+      }                                                                     \
+    }
+
 template <int MASK, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -1811,39 +1779,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
     const long qstep = (long)64 * q_ss;
     const long dostep = (long)64 * do_ss;
 
-#define BV_STAGE_IN(BUFI, QT)                                               \
-    {                                                                       \
-      _Pragma("unroll")                                                     \
-      for (int i = 0; i < 2; ++i) {                                         \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
-            16, 0, 0);                                                      \
-        qgp[i] += qstep;                                                    \
-      }                                                                     \
-      dtst[0] = *reinterpret_cast<const uint4*>(dtp[0]);                    \
-      dtst[1] = *reinterpret_cast<const uint4*>(dtp[1]);                    \
-      dtp[0] += dostep;                                                     \
-      dtp[1] += dostep;                                                     \
-      if (tid < 64)                                                         \
-        *reinterpret_cast<float*>(                                          \
-            &lds[BUFI][LSEOFF / 2 + tid * 2]) =                             \
-            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
-    }
-#define BV_WRITE_DOT(BUF)                                                   \
-    {                                                                       \
-      const int rp2_ = (tid >> 4) * 2;                                      \
-      const int c8_ = (tid & 15) * 8;                                       \
-      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
-      va_.u4 = dtst[0];                                                     \
-      vb_.u4 = dtst[1];                                                     \
-      _Pragma("unroll")                                                     \
-      for (int j = 0; j < 8; ++j) {                                         \
-        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
-        *reinterpret_cast<u32*>(&(BUF)[DOTOFF + vt_byte(c8_ + j, rp2_)]) =  \
-            pair_;                                                          \
-      }                                                                     \
-    }
-
     BV_STAGE_IN(0, qt0)
     BV_WRITE_DOT(lds0)
     __syncthreads();
@@ -1928,8 +1863,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dvrow, dvacc[ds], ds, hi);
 }
-#undef BV_STAGE_IN
-#undef BV_WRITE_DOT
 
 // ---------------------------------------------------------------------------
 // dK kernel: same kv-block walk as dV.
@@ -1946,6 +1879,52 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_kernel(
 #define BK_LSE_U16 128
 #define BK_DLT_U16 128
 #define BK_BUF_U16 (BK_Q_U16 + BK_DO_U16 + BK_QT_U16 + BK_LSE_U16 + BK_DLT_U16)
+
+// Staging of one q tile for the dK walks (attn_bwd_dk_kernel and
+// attn_bwd_dk_pair_kernel): Q and dO rows by glds, the two Q rows of the lane
+// into qtst, the lse and delta tiles; then qtst into the transposed Q image.
+// Macros over the names in scope, as BV_STAGE_IN.
+#define BK_STAGE_IN(BUFI, QT)                                               \
+    {                                                                       \
+      _Pragma("unroll")                                                     \
+      for (int i = 0; i < 2; ++i) {                                         \
+        __builtin_amdgcn_global_load_lds(                                   \
+            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
+            16, 0, 0);                                                      \
+        qgp[i] += qstep;                                                    \
+        __builtin_amdgcn_global_load_lds(                                   \
+            (const u32*)dgp[i],                                             \
+            (u32*)&lds[BUFI][DOOFF / 2 + (i * 512 + wu64 * 64) * 8],        \
+            16, 0, 0);                                                      \
+        dgp[i] += dostep;                                                   \
+      }                                                                     \
+      qtst[0] = *reinterpret_cast<const uint4*>(qtp[0]);                    \
+      qtst[1] = *reinterpret_cast<const uint4*>(qtp[1]);                    \
+      qtp[0] += qstep;                                                      \
+      qtp[1] += qstep;                                                      \
+      if (tid < 64)                                                         \
+        *reinterpret_cast<float*>(&lds[BUFI][LSEOFF / 2 + tid * 2]) =       \
+            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
+      else if (tid < 128)                                                   \
+        *reinterpret_cast<float*>(                                          \
+            &lds[BUFI][DLTOFF / 2 + (tid - 64) * 2]) =                      \
+            dbase[(QT) * 64 + tid - 64];                                    \
+    }
+#define BK_WRITE_QT(BUF)                                                    \
+    {                                                                       \
+      const int rp2_ = (tid >> 4) * 2;                                      \
+      const int c8_ = (tid & 15) * 8;                                       \
+      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
+      va_.u4 = qtst[0];                                                     \
+      vb_.u4 = qtst[1];                                                     \
+      _Pragma("unroll")                                                     \
+      for (int j = 0; j < 8; ++j) {                                         \
+        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
+        *reinterpret_cast<u32*>(&(BUF)[QTOFF + vt_byte(c8_ + j, rp2_)]) =   \
+            pair_;                                                          \
+      }                                                                     \
+    }
+
 template <int MASK, bool SPLIT>
 __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -2048,47 +2027,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
     const long qstep = (long)64 * q_ss;
     const long dostep = (long)64 * do_ss;
 
-#define BK_STAGE_IN(BUFI, QT)                                               \
-    {                                                                       \
-      _Pragma("unroll")                                                     \
-      for (int i = 0; i < 2; ++i) {                                         \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
-            16, 0, 0);                                                      \
-        qgp[i] += qstep;                                                    \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)dgp[i],                                             \
-            (u32*)&lds[BUFI][DOOFF / 2 + (i * 512 + wu64 * 64) * 8],        \
-            16, 0, 0);                                                      \
-        dgp[i] += dostep;                                                   \
-      }                                                                     \
-      qtst[0] = *reinterpret_cast<const uint4*>(qtp[0]);                    \
-      qtst[1] = *reinterpret_cast<const uint4*>(qtp[1]);                    \
-      qtp[0] += qstep;                                                      \
-      qtp[1] += qstep;                                                      \
-      if (tid < 64)                                                         \
-        *reinterpret_cast<float*>(&lds[BUFI][LSEOFF / 2 + tid * 2]) =       \
-            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
-      else if (tid < 128)                                                   \
-        *reinterpret_cast<float*>(                                          \
-            &lds[BUFI][DLTOFF / 2 + (tid - 64) * 2]) =                      \
-            dbase[(QT) * 64 + tid - 64];                                    \
-    }
-#define BK_WRITE_QT(BUF)                                                    \
-    {                                                                       \
-      const int rp2_ = (tid >> 4) * 2;                                      \
-      const int c8_ = (tid & 15) * 8;                                       \
-      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
-      va_.u4 = qtst[0];                                                     \
-      vb_.u4 = qtst[1];                                                     \
-      _Pragma("unroll")                                                     \
-      for (int j = 0; j < 8; ++j) {                                         \
-        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
-        *reinterpret_cast<u32*>(&(BUF)[QTOFF + vt_byte(c8_ + j, rp2_)]) =   \
-            pair_;                                                          \
-      }                                                                     \
-    }
-
     BK_STAGE_IN(0, qt0)
     BK_WRITE_QT(lds0)
     __syncthreads();
@@ -2174,8 +2112,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_kernel(
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) attn_store_bf16(dkrow, dkacc[ds], ds, hi);
 }
-#undef BK_STAGE_IN
-#undef BK_WRITE_QT
 
 // ---------------------------------------------------------------------------
 // dV and dK with PAIR ownership (attn_bwd_pair): causal, unsplit. Same grid,
@@ -2273,42 +2209,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
       const long qstep = (long)64 * q_ss;
       const long dostep = (long)64 * do_ss;
 
-// the staging of attn_bwd_dv_kernel, repeated: as shared functions it changed
-// the instruction stream of all four dv/dk kernels and cost this one 1 %
-// (profiles/r09_attention_refactor.md)
-#define BV_STAGE_IN(BUFI, QT)                                               \
-    {                                                                       \
-      _Pragma("unroll")                                                     \
-      for (int i = 0; i < 2; ++i) {                                         \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
-            16, 0, 0);                                                      \
-        qgp[i] += qstep;                                                    \
-      }                                                                     \
-      dtst[0] = *reinterpret_cast<const uint4*>(dtp[0]);                    \
-      dtst[1] = *reinterpret_cast<const uint4*>(dtp[1]);                    \
-      dtp[0] += dostep;                                                     \
-      dtp[1] += dostep;                                                     \
-      if (tid < 64)                                                         \
-        *reinterpret_cast<float*>(                                          \
-            &lds[BUFI][LSEOFF / 2 + tid * 2]) =                             \
-            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
-    }
-#define BV_WRITE_DOT(BUF)                                                   \
-    {                                                                       \
-      const int rp2_ = (tid >> 4) * 2;                                      \
-      const int c8_ = (tid & 15) * 8;                                       \
-      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
-      va_.u4 = dtst[0];                                                     \
-      vb_.u4 = dtst[1];                                                     \
-      _Pragma("unroll")                                                     \
-      for (int j = 0; j < 8; ++j) {                                         \
-        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
-        *reinterpret_cast<u32*>(&(BUF)[DOTOFF + vt_byte(c8_ + j, rp2_)]) =  \
-            pair_;                                                          \
-      }                                                                     \
-    }
-
       BV_STAGE_IN(0, qt0)
       BV_WRITE_DOT(lds0)
       __syncthreads();
@@ -2401,8 +2301,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dv_pair_kernel(
     }
   }
 }
-#undef BV_STAGE_IN
-#undef BV_WRITE_DOT
 
 __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,
@@ -2491,50 +2389,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
       }
       const long qstep = (long)64 * q_ss;
       const long dostep = (long)64 * do_ss;
-
-// the staging of attn_bwd_dk_kernel, repeated: as shared functions it changed
-// the instruction stream of all four dv/dk kernels and cost this one 1 %
-// (profiles/r09_attention_refactor.md)
-#define BK_STAGE_IN(BUFI, QT)                                               \
-    {                                                                       \
-      _Pragma("unroll")                                                     \
-      for (int i = 0; i < 2; ++i) {                                         \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)qgp[i], (u32*)&lds[BUFI][(i * 512 + wu64 * 64) * 8],\
-            16, 0, 0);                                                      \
-        qgp[i] += qstep;                                                    \
-        __builtin_amdgcn_global_load_lds(                                   \
-            (const u32*)dgp[i],                                             \
-            (u32*)&lds[BUFI][DOOFF / 2 + (i * 512 + wu64 * 64) * 8],        \
-            16, 0, 0);                                                      \
-        dgp[i] += dostep;                                                   \
-      }                                                                     \
-      qtst[0] = *reinterpret_cast<const uint4*>(qtp[0]);                    \
-      qtst[1] = *reinterpret_cast<const uint4*>(qtp[1]);                    \
-      qtp[0] += qstep;                                                      \
-      qtp[1] += qstep;                                                      \
-      if (tid < 64)                                                         \
-        *reinterpret_cast<float*>(&lds[BUFI][LSEOFF / 2 + tid * 2]) =       \
-            lbase[(QT) * 64 + tid] * ATTN_LOG2E;                   \
-      else if (tid < 128)                                                   \
-        *reinterpret_cast<float*>(                                          \
-            &lds[BUFI][DLTOFF / 2 + (tid - 64) * 2]) =                      \
-            dbase[(QT) * 64 + tid - 64];                                    \
-    }
-#define BK_WRITE_QT(BUF)                                                    \
-    {                                                                       \
-      const int rp2_ = (tid >> 4) * 2;                                      \
-      const int c8_ = (tid & 15) * 8;                                       \
-      union { uint4 u4; u16 h[8]; } va_, vb_;                               \
-      va_.u4 = qtst[0];                                                     \
-      vb_.u4 = qtst[1];                                                     \
-      _Pragma("unroll")                                                     \
-      for (int j = 0; j < 8; ++j) {                                         \
-        const u32 pair_ = (u32)va_.h[j] | ((u32)vb_.h[j] << 16);            \
-        *reinterpret_cast<u32*>(&(BUF)[QTOFF + vt_byte(c8_ + j, rp2_)]) =   \
-            pair_;                                                          \
-      }                                                                     \
-    }
 
       BK_STAGE_IN(0, qt0)
       BK_WRITE_QT(lds0)
@@ -2630,6 +2484,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
     }
   }
 }
+#undef BV_STAGE_IN
+#undef BV_WRITE_DOT
 #undef BK_STAGE_IN
 #undef BK_WRITE_QT
 

@@ -1071,6 +1071,21 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(
 
 #define ADEC_CHUNK 64
 #define ADEC_D 128
+#define APG_ROWS 64                  // rows of a cache page == ADEC_CHUNK
+
+// Paged addressing (see "Paged decode" below): everything read from pos or
+// the block table is clamped before it forms an address.
+__device__ __forceinline__ long apg_clamp_pos(long pos, int max_pages) {
+  const long top = (long)max_pages * APG_ROWS - 1;
+  return pos > top ? top : pos;
+}
+
+__device__ __forceinline__ int apg_phys_page(
+    const int* __restrict__ table, int b, int max_pages, int page,
+    int n_pages) {
+  const int p = table[(long)b * max_pages + page];
+  return p < 0 ? 0 : (p >= n_pages ? n_pages - 1 : p);
+}
 
 // grid (n_kv * G, n_chunk, B), ONE 64-thread wave per (kv head, q head,
 // 64-row cache chunk): at decode batch sizes the whole chip is idle, so
@@ -1078,19 +1093,37 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(
 // chunk gives 8x the workgroups of the first version (which ran 40 WGs
 // at b1 and was latency-bound at 18 us) for a trivial re-read of the
 // tiny K rows. Phase A: lane <-> cache row; phase B: lane <-> d pair.
+// PAGED: pos_dev is [B], the chunk is logical page blockIdx.y of slot b
+// (n_chunk == max_pages, Lmax unused) and its rows come through the block
+// table. A wave whose page starts beyond pos[b] (or whose slot is idle)
+// returns before it touches the table, the pools or the partial buffer.
+template <bool PAGED>
 __global__ __launch_bounds__(64) void attn_decode_partial_kernel(
     const u16* __restrict__ q,       // [B, n_kv*G, D]
-    const u16* __restrict__ kc,      // [B, n_kv, Lmax, D]
-    const u16* __restrict__ vc,
+    const u16* __restrict__ kc,      // [B, n_kv, Lmax, D] or the page pool
+    const u16* __restrict__ vc,      //   [n_pages, n_kv, 64, D]
     const long* __restrict__ pos_dev,
     float* __restrict__ partial,     // [B, n_kv, n_chunk, G, D+2]
-    int n_kv, int G, int Lmax, int n_chunk, float scale) {
+    int n_kv, int G, int Lmax, int n_chunk, float scale,
+    const int* __restrict__ table,   // [B, n_chunk] (PAGED)
+    int n_pages) {
   const int hkv = blockIdx.x / G;
   const int g = blockIdx.x % G;
   const int chunk = blockIdx.y;
   const int b = blockIdx.z;
   const int tid = threadIdx.x;
-  const long pos = *pos_dev;               // rows 0..pos are valid
+  long pos;                                // rows 0..pos are valid
+  long pbase = 0;                          // PAGED: the page's first element
+  if constexpr (PAGED) {
+    pos = pos_dev[b];
+    if (pos < 0) return;
+    pos = apg_clamp_pos(pos, n_chunk);
+    if ((long)chunk * ADEC_CHUNK > pos) return;
+    const int page = apg_phys_page(table, b, n_chunk, chunk, n_pages);
+    pbase = ((long)page * n_kv + hkv) * APG_ROWS * ADEC_D;
+  } else {
+    pos = *pos_dev;
+  }
   __shared__ float sp[ADEC_CHUNK];         // scores, then p
   __shared__ u16 qs[ADEC_D];
   reinterpret_cast<u32*>(qs)[tid] = reinterpret_cast<const u32*>(
@@ -1098,8 +1131,10 @@ __global__ __launch_bounds__(64) void attn_decode_partial_kernel(
   __syncthreads();
 
   const long row = (long)chunk * ADEC_CHUNK + tid;
-  if (row <= pos && row < Lmax) {
-    const u16* krow = kc + (((long)b * n_kv + hkv) * Lmax + row) * ADEC_D;
+  if (row <= pos && (PAGED || row < Lmax)) {
+    const u16* krow = PAGED
+        ? kc + pbase + (long)tid * ADEC_D
+        : kc + (((long)b * n_kv + hkv) * Lmax + row) * ADEC_D;
     float sx = 0.f;
     union V8 { uint4 u; u16 h[8]; };
 #pragma unroll 4
@@ -1127,9 +1162,10 @@ __global__ __launch_bounds__(64) void attn_decode_partial_kernel(
   // phase B: lane <-> d pair; v reads coalesce per row (64 x u32)
   const long lim = pos + 1 - (long)chunk * ADEC_CHUNK;
   const int nrow = lim < 0 ? 0 : (lim < ADEC_CHUNK ? (int)lim : ADEC_CHUNK);
-  const u16* vbase = vc
-      + (((long)b * n_kv + hkv) * Lmax + (long)chunk * ADEC_CHUNK) * ADEC_D
-      + tid * 2;
+  const u16* vbase = PAGED
+      ? vc + pbase + tid * 2
+      : vc + (((long)b * n_kv + hkv) * Lmax + (long)chunk * ADEC_CHUNK)
+          * ADEC_D + tid * 2;
   float a0 = 0.f, a1 = 0.f;
   for (int r = 0; r < nrow; ++r) {
     const float p = sp[r];
@@ -1152,23 +1188,37 @@ __global__ __launch_bounds__(64) void attn_decode_partial_kernel(
   }
 }
 
-// grid (B * H), 128 threads: merge the chunks for one (b, head).
+// grid (B * H), 128 threads: merge the chunks for one (b, head). PAGED
+// merges pages 0..pos[b]/64 only, in the same ascending order, and an idle
+// slot stores zeros: the chunks beyond the fill carry w = exp(-1e30 - M) = 0
+// in the contiguous merge, so leaving them out changes no bit.
+template <bool PAGED>
 __global__ __launch_bounds__(128) void attn_decode_combine_kernel(
     const float* __restrict__ partial, u16* __restrict__ o,
-    int n_kv, int G, int n_chunk) {
+    int n_kv, int G, int n_chunk,
+    const long* __restrict__ pos_dev) {   // [B] (PAGED)
   const int head = blockIdx.x;          // b * (n_kv*G) + hkv*G + g
   const int H = n_kv * G;
   const int b = head / H;
   const int hkv = (head % H) / G;
   const int g = head % G;
   const int tid = threadIdx.x;          // <-> d
+  int n_merge = n_chunk;
+  if constexpr (PAGED) {
+    const long pos = pos_dev[b];
+    if (pos < 0) {
+      o[(long)head * ADEC_D + tid] = 0;
+      return;
+    }
+    n_merge = (int)(apg_clamp_pos(pos, n_chunk) / ADEC_CHUNK) + 1;
+  }
   const float* base = partial
       + (((long)b * n_kv + hkv) * n_chunk * G + g) * (ADEC_D + 2);
   float M = -1e30f;
-  for (int c = 0; c < n_chunk; ++c)
+  for (int c = 0; c < n_merge; ++c)
     M = fmaxf(M, base[(long)c * G * (ADEC_D + 2) + ADEC_D]);
   float L = 0.f, od = 0.f;
-  for (int c = 0; c < n_chunk; ++c) {
+  for (int c = 0; c < n_merge; ++c) {
     const float* pc = base + (long)c * G * (ADEC_D + 2);
     const float w = __expf(pc[ADEC_D] - M);
     L += w * pc[ADEC_D + 1];
@@ -1265,175 +1315,46 @@ __global__ void rope_cache_kernel(
 
 
 // ---------------------------------------------------------------------------
-// Paged decode: the two kernels above with a position PER SEQUENCE and the
-// cache cut into 64-row pages (APG_ROWS == ADEC_CHUNK, so one flash-decoding
-// wave owns exactly one page and the per-chunk arithmetic is the contiguous
-// kernel's, statement for statement: a page-permuted cache gives the same
-// bits as attn_decode). Pools are [n_pages, n_kv, 64, D]; block_table
-// [B, max_pages] int32 maps logical page j of slot b to a physical page;
-// pos [B] int64 is the row this step's token occupies (rows 0..pos[b] are
-// valid), negative = idle slot. b and the page come from blockIdx, so the
-// pos and table reads are wave-uniform scalar loads: one each per wave.
-// Everything read from pos/table is clamped before it forms an address
-// (pos < max_pages*64, page into [0, n_pages)), so any table content is
-// memory-safe; only a valid table gives a meaningful result.
+// Paged decode: attn_decode_partial_kernel<true> / attn_decode_combine_kernel
+// <true> above and the rope + cache write below, with a position PER
+// SEQUENCE and the cache cut into 64-row pages (APG_ROWS == ADEC_CHUNK, so
+// one flash-decoding wave owns exactly one page and a page-permuted cache
+// gives the same bits as attn_decode). Pools are [n_pages, n_kv, 64, D];
+// block_table [B, max_pages] int32 maps logical page j of slot b to a
+// physical page; pos [B] int64 is the row this step's token occupies (rows
+// 0..pos[b] are valid), negative = idle slot. b and the page come from
+// blockIdx, so the pos and table reads are wave-uniform scalar loads: one
+// each per wave. Everything read from pos/table is clamped before it forms
+// an address (pos < max_pages*64, page into [0, n_pages)), so any table
+// content is memory-safe; only a valid table gives a meaningful result.
 // ---------------------------------------------------------------------------
 
-#define APG_ROWS 64
-
-__device__ __forceinline__ long apg_clamp_pos(long pos, int max_pages) {
-  const long top = (long)max_pages * APG_ROWS - 1;
-  return pos > top ? top : pos;
-}
-
-__device__ __forceinline__ int apg_phys_page(
-    const int* __restrict__ table, int b, int max_pages, int page,
-    int n_pages) {
-  const int p = table[(long)b * max_pages + page];
-  return p < 0 ? 0 : (p >= n_pages ? n_pages - 1 : p);
-}
-
-// grid (n_kv * G, max_pages, B), one 64-thread wave per (q head, page). A
-// wave whose page starts beyond pos[b] (or whose slot is idle) returns
-// before it touches the table, the pools or the partial buffer.
-__global__ __launch_bounds__(64) void attn_decode_paged_partial_kernel(
-    const u16* __restrict__ q,       // [B, n_kv*G, D]
-    const u16* __restrict__ kp,      // [n_pages, n_kv, 64, D]
-    const u16* __restrict__ vp,
-    const int* __restrict__ table,   // [B, max_pages]
-    const long* __restrict__ pos_dev,  // [B]
-    float* __restrict__ partial,     // [B, n_kv, max_pages, G, D+2]
-    int n_kv, int G, int n_pages, int max_pages, float scale) {
-  const int hkv = blockIdx.x / G;
-  const int g = blockIdx.x % G;
-  const int chunk = blockIdx.y;
-  const int b = blockIdx.z;
-  const int tid = threadIdx.x;
-  long pos = pos_dev[b];                   // rows 0..pos are valid
-  if (pos < 0) return;
-  pos = apg_clamp_pos(pos, max_pages);
-  if ((long)chunk * ADEC_CHUNK > pos) return;
-  const int page = apg_phys_page(table, b, max_pages, chunk, n_pages);
-  const long pbase = ((long)page * n_kv + hkv) * APG_ROWS * ADEC_D;
-  __shared__ float sp[ADEC_CHUNK];         // scores, then p
-  __shared__ u16 qs[ADEC_D];
-  reinterpret_cast<u32*>(qs)[tid] = reinterpret_cast<const u32*>(
-      q + ((long)b * n_kv * G + hkv * G + g) * ADEC_D)[tid];
-  __syncthreads();
-
-  const long row = (long)chunk * ADEC_CHUNK + tid;
-  if (row <= pos) {
-    const u16* krow = kp + pbase + (long)tid * ADEC_D;
-    float sx = 0.f;
-    union V8 { uint4 u; u16 h[8]; };
-#pragma unroll 4
-    for (int c = 0; c < ADEC_D; c += 8) {
-      V8 kv8;
-      kv8.u = *reinterpret_cast<const uint4*>(krow + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) sx += bf2f(qs[c + j]) * bf2f(kv8.h[j]);
-    }
-    sp[tid] = sx * scale;
-  } else {
-    sp[tid] = -1e30f;
-  }
-  __syncthreads();
-
-  float m = -1e30f;
-  for (int r = 0; r < ADEC_CHUNK; ++r) m = fmaxf(m, sp[r]);
-  const float pv = (sp[tid] > -1e30f) ? __expf(sp[tid] - m) : 0.f;
-  __syncthreads();
-  sp[tid] = pv;
-  __syncthreads();
-
-  const long lim = pos + 1 - (long)chunk * ADEC_CHUNK;
-  const int nrow = lim < 0 ? 0 : (lim < ADEC_CHUNK ? (int)lim : ADEC_CHUNK);
-  const u16* vbase = vp + pbase + tid * 2;
-  float a0 = 0.f, a1 = 0.f;
-  for (int r = 0; r < nrow; ++r) {
-    const float p = sp[r];
-    union { u32 w; u16 h[2]; } vv;
-    vv.w = *reinterpret_cast<const u32*>(vbase + (long)r * ADEC_D);
-    a0 += p * bf2f(vv.h[0]);
-    a1 += p * bf2f(vv.h[1]);
-  }
-
-  float* out = partial
-      + ((((long)b * n_kv + hkv) * max_pages + chunk) * G + g)
-      * (ADEC_D + 2);
-  out[tid * 2] = a0;
-  out[tid * 2 + 1] = a1;
-  if (tid == 0) {
-    float l = 0.f;
-    for (int r = 0; r < ADEC_CHUNK; ++r) l += sp[r];
-    out[ADEC_D] = m;
-    out[ADEC_D + 1] = l;
-  }
-}
-
-// grid (B * H), 128 threads: merge pages 0..pos[b]/64 of one (b, head) in
-// ascending order; an idle slot stores zeros. The pages beyond the fill
-// carried w = exp(-1e30 - M) = 0 in the contiguous combine, so leaving
-// them out changes no bit.
-__global__ __launch_bounds__(128) void attn_decode_paged_combine_kernel(
-    const float* __restrict__ partial, const long* __restrict__ pos_dev,
-    u16* __restrict__ o, int n_kv, int G, int max_pages) {
-  const int head = blockIdx.x;          // b * (n_kv*G) + hkv*G + g
-  const int H = n_kv * G;
-  const int b = head / H;
-  const int hkv = (head % H) / G;
-  const int g = head % G;
-  const int tid = threadIdx.x;          // <-> d
-  long pos = pos_dev[b];
-  if (pos < 0) {
-    o[(long)head * ADEC_D + tid] = 0;
-    return;
-  }
-  pos = apg_clamp_pos(pos, max_pages);
-  const int n_chunk = (int)(pos / ADEC_CHUNK) + 1;
-  const float* base = partial
-      + (((long)b * n_kv + hkv) * max_pages * G + g) * (ADEC_D + 2);
-  float M = -1e30f;
-  for (int c = 0; c < n_chunk; ++c)
-    M = fmaxf(M, base[(long)c * G * (ADEC_D + 2) + ADEC_D]);
-  float L = 0.f, od = 0.f;
-  for (int c = 0; c < n_chunk; ++c) {
-    const float* pc = base + (long)c * G * (ADEC_D + 2);
-    const float w = __expf(pc[ADEC_D] - M);
-    L += w * pc[ADEC_D + 1];
-    od += w * pc[tid];
-  }
-  o[(long)head * ADEC_D + tid] = f2bf(od / fmaxf(L, 1e-30f));
-}
-
-// rope_cache_kernel with the k/v destination pool[table[b][pos/64]][hkv]
-// [pos%64] and the angle from pos[b]. An idle slot writes no k/v and
-// zeros its q rows.
-__global__ void rope_cache_paged_kernel(
+// One (token row, head) of the paged rope + cache write: rope_cache_kernel
+// with the k/v destination pool[table[b][pos/64]][hkv][pos%64]. row indexes
+// the packed qkv and qout rows, b the block table, hx is 0..nh-1 q, ..+nkv
+// k, ..+nkv v, and lane d holds the (d, d+D/2) pair. pos < 0 (idle slot,
+// padding token) writes no k/v and zeros the q rows.
+__device__ __forceinline__ void rope_cache_paged_row(
     const u16* __restrict__ qkv, u16* __restrict__ qout,
     u16* __restrict__ kpool, u16* __restrict__ vpool,
     const float* __restrict__ inv_freq, const int* __restrict__ table,
-    const long* __restrict__ pos_dev, int nh, int nkv, int n_pages,
+    long row, int b, long pos, int hx, int d, int nh, int nkv, int n_pages,
     int max_pages, int D) {
-  const int hx = blockIdx.x;             // 0..nh-1 q, ..+nkv k, ..+nkv v
-  const int b = blockIdx.y;
-  const int d = threadIdx.x;             // 0 .. D/2-1
   const int half = D / 2;
-  long pos = pos_dev[b];
   if (pos < 0) {
     if (hx < nh) {
-      u16* z = qout + ((long)b * nh + hx) * D;
+      u16* z = qout + (row * nh + hx) * D;
       z[d] = 0;
       z[d + half] = 0;
     }
     return;
   }
   pos = apg_clamp_pos(pos, max_pages);
-  const u16* src = qkv + ((long)b * (nh + 2 * nkv)) * D + (long)hx * D;
+  const u16* src = qkv + (row * (nh + 2 * nkv)) * D + (long)hx * D;
   const float x1 = bf2f(src[d]), x2 = bf2f(src[d + half]);
   u16* dst;
   if (hx < nh) {
-    dst = qout + ((long)b * nh + hx) * D;
+    dst = qout + (row * nh + hx) * D;
   } else {
     const int page = apg_phys_page(table, b, max_pages,
                                    (int)(pos / APG_ROWS), n_pages);
@@ -1454,13 +1375,25 @@ __global__ void rope_cache_paged_kernel(
   dst[d + half] = f2bf(x1 * sn + x2 * c);
 }
 
-// rope_cache_paged_kernel for T packed tokens of several sequences (paged
-// prefill): token t belongs to slot tok_slot[t] and sits at cache position
+// One decode token per slot: grid (nh + 2*nkv, B), the angle from pos[b].
+__global__ void rope_cache_paged_kernel(
+    const u16* __restrict__ qkv, u16* __restrict__ qout,
+    u16* __restrict__ kpool, u16* __restrict__ vpool,
+    const float* __restrict__ inv_freq, const int* __restrict__ table,
+    const long* __restrict__ pos_dev, int nh, int nkv, int n_pages,
+    int max_pages, int D) {
+  const int b = blockIdx.y;
+  rope_cache_paged_row(qkv, qout, kpool, vpool, inv_freq, table, b, b,
+                       pos_dev[b], blockIdx.x, threadIdx.x, nh, nkv,
+                       n_pages, max_pages, D);
+}
+
+// T packed tokens of several sequences (paged prefill): grid (T, nh +
+// 2*nkv); token t belongs to slot tok_slot[t] and sits at cache position
 // tok_pos[t]. Same angle expression, so a row written here is the row the
-// decode kernel would have written. A token with tok_pos < 0 writes no k/v
-// and zeros its q rows. The slot is clamped into [0, B) next to the
-// position and page clamps: any tok_slot/tok_pos/table content is
-// memory-safe.
+// decode kernel would have written. The slot is clamped into [0, B) next to
+// the position and page clamps: any tok_slot/tok_pos/table content is
+// memory-safe. A padding token (tok_pos < 0) reads no tok_slot entry.
 __global__ void rope_cache_paged_rows_kernel(
     const u16* __restrict__ qkv, u16* __restrict__ qout,
     u16* __restrict__ kpool, u16* __restrict__ vpool,
@@ -1468,44 +1401,12 @@ __global__ void rope_cache_paged_rows_kernel(
     const int* __restrict__ tok_slot, const long* __restrict__ tok_pos,
     int B, int nh, int nkv, int n_pages, int max_pages, int D) {
   const int t = blockIdx.x;
-  const int hx = blockIdx.y;             // 0..nh-1 q, ..+nkv k, ..+nkv v
-  const int d = threadIdx.x;             // 0 .. D/2-1
-  const int half = D / 2;
-  long pos = tok_pos[t];
-  if (pos < 0) {
-    if (hx < nh) {
-      u16* z = qout + ((long)t * nh + hx) * D;
-      z[d] = 0;
-      z[d + half] = 0;
-    }
-    return;
-  }
-  pos = apg_clamp_pos(pos, max_pages);
-  int b = tok_slot[t];
+  const long pos = tok_pos[t];
+  int b = pos < 0 ? 0 : tok_slot[t];
   b = b < 0 ? 0 : (b >= B ? B - 1 : b);
-  const u16* src = qkv + ((long)t * (nh + 2 * nkv)) * D + (long)hx * D;
-  const float x1 = bf2f(src[d]), x2 = bf2f(src[d + half]);
-  u16* dst;
-  if (hx < nh) {
-    dst = qout + ((long)t * nh + hx) * D;
-  } else {
-    const int page = apg_phys_page(table, b, max_pages,
-                                   (int)(pos / APG_ROWS), n_pages);
-    const int r = (int)(pos % APG_ROWS);
-    if (hx < nh + nkv) {
-      dst = kpool + ((((long)page * nkv + (hx - nh)) * APG_ROWS) + r) * D;
-    } else {
-      u16* vd = vpool
-          + ((((long)page * nkv + (hx - nh - nkv)) * APG_ROWS) + r) * D;
-      vd[d] = src[d];
-      vd[d + half] = src[d + half];
-      return;
-    }
-  }
-  float c, sn;
-  __sincosf((float)pos * inv_freq[d], &sn, &c);
-  dst[d] = f2bf(x1 * c - x2 * sn);
-  dst[d + half] = f2bf(x1 * sn + x2 * c);
+  rope_cache_paged_row(qkv, qout, kpool, vpool, inv_freq, table, t, b, pos,
+                       blockIdx.y, threadIdx.x, nh, nkv, n_pages, max_pages,
+                       D);
 }
 
 
@@ -2080,13 +1981,15 @@ int attn_decode(void* stream, const void* q, const void* kc,
     return -1;
   const int G = H / n_kv;
   dim3 grid((unsigned)(n_kv * G), (unsigned)n_chunk, (unsigned)B);
-  hipLaunchKernelGGL(attn_decode_partial_kernel, grid, dim3(64), 0,
+  hipLaunchKernelGGL(attn_decode_partial_kernel<false>, grid, dim3(64), 0,
                      STREAM, (const u16*)q, (const u16*)kc,
                      (const u16*)vc, (const long*)pos_dev,
-                     (float*)partial, n_kv, G, Lmax, n_chunk, scale);
-  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)(B * H)),
-                     dim3(128), 0, STREAM, (const float*)partial, (u16*)o,
-                     n_kv, G, n_chunk);
+                     (float*)partial, n_kv, G, Lmax, n_chunk, scale,
+                     (const int*)nullptr, 0);
+  hipLaunchKernelGGL(attn_decode_combine_kernel<false>,
+                     dim3((unsigned)(B * H)), dim3(128), 0, STREAM,
+                     (const float*)partial, (u16*)o, n_kv, G, n_chunk,
+                     (const long*)nullptr);
   return 0;
 }
 
@@ -2158,15 +2061,15 @@ int attn_decode_paged(void* stream, const void* q, const void* k_pool,
     return -1;
   const int G = H / n_kv;
   dim3 grid((unsigned)(n_kv * G), (unsigned)max_pages, (unsigned)B);
-  hipLaunchKernelGGL(attn_decode_paged_partial_kernel, grid, dim3(64), 0,
+  hipLaunchKernelGGL(attn_decode_partial_kernel<true>, grid, dim3(64), 0,
                      STREAM, (const u16*)q, (const u16*)k_pool,
-                     (const u16*)v_pool, (const int*)block_table,
-                     (const long*)pos_dev, (float*)partial, n_kv, G,
-                     n_pages, max_pages, scale);
-  hipLaunchKernelGGL(attn_decode_paged_combine_kernel,
+                     (const u16*)v_pool, (const long*)pos_dev,
+                     (float*)partial, n_kv, G, /*Lmax=*/0, max_pages, scale,
+                     (const int*)block_table, n_pages);
+  hipLaunchKernelGGL(attn_decode_combine_kernel<true>,
                      dim3((unsigned)(B * H)), dim3(128), 0, STREAM,
-                     (const float*)partial, (const long*)pos_dev, (u16*)o,
-                     n_kv, G, max_pages);
+                     (const float*)partial, (u16*)o, n_kv, G, max_pages,
+                     (const long*)pos_dev);
   return 0;
 }
 
