@@ -6,7 +6,8 @@ families an OpenAI-ish token-in/token-out endpoint on an MI355X node:
 
     python -m trainingjob_operator_amd.launcher.serve \
         --model llama3-8b --port 8000 [--ckpt-dir DIR] [--graph]
-        [--paged [--max-slots N] [--pool-pages N] [--prefill-chunk N]]
+        [--paged [--max-slots N] [--pool-pages N] [--prefill-chunk N]
+         [--lookup-k N]]
 
 The API is deliberately token-level (``prompt_tokens`` → ``tokens``):
 tokenizers are workload assets the cluster may not have offline, and the
@@ -22,7 +23,10 @@ lengths are accepted, every sequence is its own engine request, and
 concurrent HTTP requests share decode steps rather than queueing.
 --prefill-chunk N (N > 0) also prefills inside the engine, straight into
 the pages, at most N prompt tokens per step; 0 (default) prefills every
-request at once on a temporary contiguous cache.
+request at once on a temporary contiguous cache. --lookup-k N (1..7)
+makes every decode step a speculative verify step: greedy requests draft
+up to N tokens by prompt lookup and all slots verify them in one forward
+(same tokens, fewer steps; not together with --graph).
 
 Endpoints:
     GET  /healthz   liveness + model name
@@ -50,13 +54,13 @@ _PAGED_GAUGES = {}
 
 def create_app(model, model_name: str = "model", paged: bool = False,
                max_slots: int = 8, pool_pages: Optional[int] = None,
-               prefill_chunk: int = 0):
+               prefill_chunk: int = 0, lookup_k: int = 0):
     """Build the FastAPI app around an already-constructed model (tests
     pass a CPU llama-tiny; the CLI builds the named config on cuda:0).
     paged=True serves /generate through a PagedEngine of `max_slots`
     sequences over `pool_pages` 64-row KV pages (default 32 per slot);
     prefill_chunk > 0 selects the engine's paged prefill with that many
-    prompt tokens per step."""
+    prompt tokens per step, lookup_k > 0 its prompt-lookup speculation."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -115,6 +119,7 @@ def create_app(model, model_name: str = "model", paged: bool = False,
         engine = PagedEngine(
             model, max_slots=max_slots, n_pages=pool_pages,
             graph=os.environ.get("AITJ_DECODE_GRAPH") == "1",
+            lookup_k=lookup_k,
             **({"prefill": "paged", "prefill_chunk": int(prefill_chunk)}
                if prefill_chunk else {}))
         if mx:
@@ -193,7 +198,8 @@ def create_app(model, model_name: str = "model", paged: bool = False,
                         pages_total=engine.cache.n_pages,
                         pages_free=engine.cache.pages_free,
                         prefill_chunk=(engine.prefill_chunk
-                                       if engine.prefill == "paged" else 0))
+                                       if engine.prefill == "paged" else 0),
+                        lookup_k=engine.lookup_k)
         return body
 
     @app.get("/metrics")
@@ -326,6 +332,10 @@ def main(argv=None):
                          "into the pages, at most N prompt tokens per step "
                          "(0 = prefill each request at once on a contiguous "
                          "cache)")
+    ap.add_argument("--lookup-k", type=int, default=0,
+                    help="with --paged: prompt-lookup speculation, up to N "
+                         "(<= 7) draft tokens per greedy request and step "
+                         "(0 = plain decode)")
     args = ap.parse_args(argv)
     if args.graph:
         os.environ["AITJ_DECODE_GRAPH"] = "1"
@@ -337,7 +347,8 @@ def main(argv=None):
         print(f"loaded checkpoint step {step} from {args.ckpt_dir}")
     app = create_app(model, args.model, paged=args.paged,
                      max_slots=args.max_slots, pool_pages=args.pool_pages,
-                     prefill_chunk=args.prefill_chunk)
+                     prefill_chunk=args.prefill_chunk,
+                     lookup_k=args.lookup_k)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 
 

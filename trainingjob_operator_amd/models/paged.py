@@ -22,6 +22,12 @@ device (ops.rope_cache_paged, ops.decode_attention_paged):
     the pages directly (ops.rope_cache_paged_rows) and attends them
     through the block table (ops.prefill_attention_paged), bounded per
     step by prefill_chunk;
+  * _verify_paged — the speculative step (PagedEngine(lookup_k=N)): up to
+    N + 1 tokens per slot in one forward, written like prefill rows
+    (ops.rope_cache_paged_rows) and attended by the split-KV multi-token
+    kernel (ops.verify_attention_paged). The engine drafts by prompt
+    lookup, accepts the matching prefix plus the bonus token and rolls
+    back by setting each slot's position;
   * generate_ragged — prompts of different lengths in, one tensor each out.
 
 Admission reserves ceil((prompt + max_new_tokens) / 64) pages up front
@@ -41,8 +47,10 @@ import torch
 
 from ..ops import (decode_attention_paged, decode_linear, fused_rmsnorm,
                    prefill_attention_paged, prefill_work, reference,
-                   rope_cache_paged, rope_cache_paged_rows)
-from .generate import KVCache, _forward_cached, _layers_cached, _sample
+                   rope_cache_paged, rope_cache_paged_rows,
+                   verify_attention_paged)
+from .generate import (KVCache, _forward_cached, _layers_cached,
+                       _ngram_proposal, _sample)
 
 PAGE_ROWS = reference.PAGE_ROWS
 
@@ -140,6 +148,11 @@ class PagedKVCache:
     def set_pos(self, slot: int, pos: int) -> None:
         self.host_pos[slot] = pos
         self.pos[slot] = pos
+
+    def sync_pos(self, host_pos: List[int]) -> None:
+        """Every slot's position at once: one copy to the device."""
+        self.host_pos = list(host_pos)
+        self.pos.copy_(torch.tensor(self.host_pos, dtype=torch.int64))
 
     def advance(self) -> None:
         """Host mirror of the step's in-kernel `pos += (pos >= 0)`."""
@@ -301,6 +314,56 @@ def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
     return logits.reshape(len(rows), -1)
 
 
+@torch.no_grad()
+def _verify_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
+                  n_q: torch.Tensor) -> torch.Tensor:
+    """One speculative verify forward for every slot of a paged cache:
+    tokens [B, T] (B = cache.max_slots, T <= 8); token t of slot b sits at
+    position cache.pos[b] + t, and only the first n_q[b] (int32 [B], device)
+    tokens of an active slot are real, whose pages the caller owns
+    (ensure_row). Every layer writes k/v of the real tokens into the pages
+    (ops.rope_cache_paged_rows with token slots and positions built on the
+    device) and attends rows 0..position (ops.verify_attention_paged).
+    Returns logits [B, T, V]; row t predicts the token after position
+    cache.pos[b] + t. Rows of idle slots and rows t >= n_q[b] are finite
+    and unused. cache.pos is read, never advanced: the caller sets each
+    slot's position to pos + 1 + accepted, and that is the whole rollback,
+    because rows beyond a position are never read."""
+    cfg = model.cfg
+    B, T = tokens.shape
+    dev = tokens.device
+    scale = 1.0 / math.sqrt(cfg.head_dim)
+    t_idx = torch.arange(T, device=dev)
+    real = (cache.pos >= 0)[:, None] & (t_idx[None, :] < n_q[:, None])
+    tok_pos = torch.where(real, cache.pos[:, None] + t_idx[None, :],
+                          torch.full_like(real, -1, dtype=torch.int64))
+    tok_slot = torch.where(
+        real, torch.arange(B, device=dev, dtype=torch.int32)[:, None],
+        torch.full_like(real, -1, dtype=torch.int32))
+    tok_pos = tok_pos.reshape(-1).contiguous()
+    tok_slot = tok_slot.reshape(-1).contiguous()
+
+    def attend(li, blk, qkv):
+        q = rope_cache_paged_rows(qkv.reshape(B * T, -1), cache.k[li],
+                                  cache.v[li], model.inv_freq,
+                                  cache.block_table, tok_slot, tok_pos,
+                                  cfg.num_heads, cfg.num_kv_heads)
+        q = q.reshape(B, T, cfg.num_heads, cfg.head_dim)
+        o = verify_attention_paged(q, cache.k[li], cache.v[li],
+                                   cache.block_table, cache.pos, n_q, scale)
+        if o is None:                 # off-GPU or head_dim != 128: twin
+            o = reference.verify_attention_paged(
+                q, cache.k[li], cache.v[li], cache.block_table, cache.pos,
+                n_q, scale)
+        return o
+
+    x, residual = _layers_cached(model, model.embed(tokens), attend)
+    normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
+                              cfg.norm_eps)
+    logits = decode_linear(normed, model.lm_head.weight)
+    return logits.reshape(B, T, -1)
+
+
 class PagedRequest:
     """One sequence in the engine. `tokens` grows from the prompt;
     `done` is set when it finished (or failed: `error`). With paged
@@ -361,13 +424,28 @@ class PagedEngine:
     prompt spans several steps while the other slots keep decoding. A
     prompt that completes gets its first token and joins the same step's
     decode. Prefill always runs eagerly, between graph replays.
+
+    lookup_k > 0 (at most 7) turns the decode step into a speculative
+    verify step: every active greedy request drafts up to lookup_k tokens
+    by prompt lookup over its own prompt and output, all slots go through
+    one _verify_paged forward, and each keeps the matching prefix plus the
+    bonus token. The tokens are those of lookup_k = 0; only the number of
+    steps changes. Eager only: with graph=True it is a ValueError.
     """
 
     def __init__(self, model, max_slots: int = 8,
                  n_pages: Optional[int] = None,
                  max_pages_per_seq: Optional[int] = None,
                  graph: bool = False, prefill: str = "contiguous",
-                 prefill_chunk: int = 512):
+                 prefill_chunk: int = 512, lookup_k: int = 0):
+        if not 0 <= lookup_k <= 7:
+            raise ValueError("lookup_k must be in 0..7")
+        if lookup_k > 0 and graph:
+            raise ValueError("lookup_k > 0 runs eagerly: graph capture of "
+                             "the verify step is not wired in yet")
+        self.lookup_k = int(lookup_k)
+        self.drafted = 0              # draft tokens verified / accepted
+        self.accepted = 0
         if prefill not in ("contiguous", "paged"):
             raise ValueError(f"prefill must be 'contiguous' or 'paged', "
                              f"not {prefill!r}")
@@ -601,6 +679,57 @@ class PagedEngine:
         self._graph = g
         self.cache.pos.copy_(saved)
 
+    def _verify_step(self, active: list, finished: list) -> None:
+        """The decode step with lookup_k > 0: draft, one _verify_paged
+        forward for all slots, accept, set the positions."""
+        cache = self.cache
+        T = self.lookup_k + 1
+        toks = [[0] * T for _ in range(self.max_slots)]
+        n_q = [1] * self.max_slots
+        drafts = {}
+        for req in active:
+            room = req.max_new_tokens - req.n_new
+            prop = []
+            if req.temperature <= 0.0 and room > 1:
+                prop = _ngram_proposal(req.tokens,
+                                       min(self.lookup_k, room - 1))
+            drafts[req.slot] = prop
+            row = [self._host_cur[req.slot]] + prop
+            toks[req.slot][:len(row)] = row
+            n_q[req.slot] = len(row)
+            # pages for every row this step writes: inside the reservation,
+            # since pos + room - 1 is the request's last row
+            cache.ensure_row(req.slot, cache.host_pos[req.slot] + len(row) - 1)
+        logits = _verify_paged(
+            self.model, torch.tensor(toks, dtype=torch.long).to(self.device),
+            cache, torch.tensor(n_q, dtype=torch.int32).to(self.device))
+        self.steps += 1
+        greedy = None
+        if any(r.temperature <= 0.0 for r in active):
+            greedy = logits.argmax(dim=-1).tolist()        # one sync
+        new_pos = list(cache.host_pos)
+        for req in active:
+            slot, prop = req.slot, drafts[req.slot]
+            if req.temperature > 0.0:
+                emitted = [self._pick(req, logits[slot, 0], None)]
+            else:
+                nxt = greedy[slot]
+                n_ok = 0
+                while n_ok < len(prop) and prop[n_ok] == nxt[n_ok]:
+                    n_ok += 1
+                emitted = nxt[:n_ok + 1]               # accepted + bonus
+                self.drafted += len(prop)
+                self.accepted += n_ok
+                if req.eos_token is not None and req.eos_token in emitted:
+                    emitted = emitted[:emitted.index(req.eos_token) + 1]
+            req.tokens.extend(emitted)
+            new_pos[slot] += len(emitted)
+            self._host_cur[slot] = emitted[-1]
+        cache.sync_pos(new_pos)
+        for req in active:
+            if req.finished:
+                self._retire(req, finished)
+
     @torch.no_grad()
     def step(self) -> List[PagedRequest]:
         """Refill free slots, decode one token per active slot; returns
@@ -615,6 +744,9 @@ class PagedEngine:
             active = [r for r in self.slots
                       if r is not None and not r.prefilling]
             if not active:
+                return finished
+            if self.lookup_k > 0:
+                self._verify_step(active, finished)
                 return finished
             for req in active:      # page for the row this step writes
                 self.cache.ensure_row(req.slot,
@@ -674,14 +806,16 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
                     seed: Optional[int] = None, max_slots: int = 8,
                     n_pages: Optional[int] = None,
                     graph: bool = False,
-                    prefill_chunk: Optional[int] = None
-                    ) -> List[torch.Tensor]:
+                    prefill_chunk: Optional[int] = None,
+                    lookup_k: int = 0) -> List[torch.Tensor]:
     """generate() for prompts of DIFFERENT lengths: every prompt is its
     own engine request (own position, own pages, own generator seeded
     with `seed`), decoded together `max_slots` at a time. Returns one
     1-D tensor (prompt + generated) per prompt, in order. prefill_chunk:
     None or 0 = prefill each prompt at once on a contiguous cache; N > 0 =
-    paged prefill, at most N prompt tokens per engine step."""
+    paged prefill, at most N prompt tokens per engine step. lookup_k > 0:
+    prompt-lookup speculation for the greedy requests (PagedEngine), same
+    tokens in fewer steps."""
     was_training = model.training
     model.eval()
     try:
@@ -693,7 +827,8 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
         paged = {"prefill": "paged", "prefill_chunk": int(prefill_chunk)} \
             if prefill_chunk else {}
         eng = PagedEngine(model, max_slots=max_slots, n_pages=n_pages,
-                          max_pages_per_seq=need, graph=graph, **paged)
+                          max_pages_per_seq=need, graph=graph,
+                          lookup_k=lookup_k, **paged)
         ids = [eng.submit(p, max_new_tokens, temperature, top_k, eos_token,
                           seed) for p in prompts]
         done = eng.run()

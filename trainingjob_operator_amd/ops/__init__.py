@@ -23,6 +23,7 @@ from .functional import (
     rope_cache_paged_rows,
     swiglu,
     swiglu_packed,
+    verify_attention_paged,
 )
 from .native import HipOpsUnavailable, available, build_ops, load
 
@@ -43,6 +44,7 @@ __all__ = [
     "rope_cache_paged",
     "rope_cache_paged_rows",
     "swiglu",
+    "verify_attention_paged",
     "available",
     "build_ops",
     "load",

@@ -456,6 +456,55 @@ def prefill_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
     return o
 
 
+def verify_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, block_table: torch.Tensor,
+                           pos: torch.Tensor, n_q: torch.Tensor,
+                           scale: float) -> Optional[torch.Tensor]:
+    """Multi-token (speculative verify) attention over a PAGED cache
+    (hip/attention.hip attn_verify_paged): q [B, T, H, D], 1 <= T <= 8,
+    already roped; token t of slot b sits at cache position pos[b] + t and
+    attends rows 0..pos[b]+t, which rope_cache_paged_rows has written.
+    pos [B] int64 is the position of the slot's FIRST token (negative =
+    idle slot), n_q [B] int32 the number of valid tokens (clamped into
+    1..T). One wave per (kv head, 32 query rows, page) on the matrix
+    units, then a log-sum-exp combine. Returns o [B, T, H, D]; rows of idle
+    slots and rows t >= n_q[b] are zeros. Same contract as
+    decode_attention_paged: None when the shape is unsupported (the caller
+    falls back to reference.verify_attention_paged), the workspace is
+    allocated here and nothing comes from the host, so the call can be
+    captured in a graph. Inference-only."""
+    if q.dim() != 4 or k_pool.dim() != 4 or block_table.dim() != 2:
+        return None
+    B, T, H, D = q.shape
+    n_pages, n_kv, R = k_pool.shape[0], k_pool.shape[1], k_pool.shape[2]
+    G = H // n_kv if H % n_kv == 0 else 0
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and D == 128
+            and 1 <= T <= 8 and G >= 1 and R == reference.PAGE_ROWS
+            and q.is_contiguous() and k_pool.dtype == torch.bfloat16
+            and k_pool.shape == v_pool.shape and k_pool.shape[3] == D
+            and k_pool.is_contiguous() and v_pool.is_contiguous()
+            and block_table.dtype == torch.int32
+            and block_table.shape[0] == B and block_table.is_contiguous()
+            and pos.dtype == torch.int64 and pos.shape == (B,)
+            and pos.is_contiguous()
+            and n_q.dtype == torch.int32 and n_q.shape == (B,)
+            and n_q.is_contiguous() and pos.is_cuda and n_q.is_cuda
+            and block_table.is_cuda):
+        return None
+    lib = _hip()
+    max_pages = block_table.shape[1]
+    ws = torch.empty(B, n_kv, max_pages, G * T, 132, dtype=torch.float32,
+                     device=q.device)
+    o = torch.empty_like(q)
+    rc = lib.attn_verify_paged(native.stream_ptr(), _ptr(q), _ptr(k_pool),
+                               _ptr(v_pool), _ptr(block_table), _ptr(pos),
+                               _ptr(n_q), _ptr(ws), _ptr(o), B, T, H, n_kv,
+                               n_pages, max_pages, scale)
+    native.check_rc(rc, "attn_verify_paged",
+                    f"T={T} H={H} n_kv={n_kv} max_pages={max_pages}")
+    return o
+
+
 def decode_swiglu(x: torch.Tensor,
                   gate_up_weight: torch.Tensor) -> Optional[torch.Tensor]:
     """silu(x @ Wg^T) * (x @ Wu^T) over the packed [2F, K] gate|up weight

@@ -1419,6 +1419,237 @@ __global__ __launch_bounds__(512) void attn_prefill_paged_kernel(
 }
 
 // ===========================================================================
+// Paged speculative VERIFY: T <= 8 draft tokens per slot against the paged
+// cache, flash-decoding over pages with the query block on the matrix units.
+//
+// q [B, T, H, 128]: token t of slot b sits at cache position pos[b] + t and
+// attends rows 0 .. pos[b] + t (its own row is already in the pages). pos [B]
+// int64 (negative = idle slot), n_q [B] int32 (valid tokens, clamped into
+// 1..T) and the block table are read on the device: no host input, so the
+// two launches replay in a graph.
+//
+// Partial kernel: ONE 64-thread wave per (kv head, tile of 32 query rows,
+// logical page, slot), grid (n_kv * ceil(G*T/32), max_pages, B). The query
+// rows of a kv head are the pairs (t, g) in t-major order r = t * G + g, so
+// the valid rows (t < n_q) are a prefix and the page is read once per kv head
+// for the whole GQA group. A wave returns before it touches the table, the
+// pools or the workspace when its slot is idle, its page starts beyond
+// pos + n_q - 1, its tile holds no valid row, or its page starts beyond the
+// position of its last row. Lanes beyond the valid rows carry the last valid
+// row and store nothing.
+//
+// S^T[kv, q] = K Q^T operand-swapped (2 kv halves x 8 k-steps of 32x32x16):
+// both operands are "row, 8 contiguous d" fragments, so K and Q go from
+// global memory straight into registers and the lane owns query row `low`:
+// page max, exp2 and row sum are lane-local plus one exchange between the
+// lane halves. Scores of kv rows beyond the row's position become -1e30 by
+// select, P is exactly 0 there. P is repacked in registers (attn_repack);
+// V goes global -> registers -> the vt_byte transposed image in LDS (the
+// wave plays the 8 thread groups of attn_write_t in turn), and
+// O^T[d, q] = V^T P^T is 4 d-tiles x 4 k-steps. Each stored row leaves an
+// unnormalised fp32 record (acc[128], m, l, 2 pad) with m in log2 units;
+// the record is 132 floats so that its float4 stores stay 16-byte aligned.
+// A row whose position lies before the page stores nothing (the combine
+// never reads that record).
+//
+// Combine kernel: one 128-thread workgroup per (b, t, q head) merges pages
+// 0 .. (pos + t) / 64 in ascending order and stores zeros for idle slots and
+// for t >= n_q.
+//
+// Clamps: pos into [0, max_pages * 64 - 1], every row position likewise, n_q
+// into [1, T], table entries into [0, n_pages) - the rules of apg_clamp_pos
+// and apg_phys_page in ops.hip - before any of them forms an address.
+//
+// Garbage contract, NaN-safe: V rows beyond pos + n_q - 1 are replaced by
+// zeros on the way into LDS and K rows there only feed scores that the select
+// replaces, so cache rows beyond a slot's last valid position, pages beyond
+// the walk and pages outside the table may hold ANY bits, NaN and Inf
+// included, without changing a bit of the output. Rows between a token's
+// position and pos + n_q - 1 are the slot's own later tokens: finite.
+//
+// Row independence: a valid row's record and output depend on that row of q,
+// its position and the cache only - not on n_q, on the other rows, or on T.
+// (The MFMA columns are independent, and the zeroed V rows meet P == 0.)
+//
+// Built without packed fp32 ops (ATTN_NO_PK_F32).
+// ===========================================================================
+
+#define ATTN_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#define AVF_ROWS 32                       // query rows of one wave
+#define AVF_REC (ATTN_D + 4)              // acc[128], m, l, 2 pad
+
+ATTN_NO_PK_F32 __global__ __launch_bounds__(64)
+void attn_verify_partial_kernel(
+    const u16* __restrict__ q,            // [B, T, H, 128]
+    const u16* __restrict__ kpool, const u16* __restrict__ vpool,
+    const long* __restrict__ pos_dev, const int* __restrict__ nq_dev,
+    const int* __restrict__ table, float* __restrict__ ws,
+    int T, int n_heads, int G, int n_kv, int n_rt, int n_pages,
+    int max_pages, float scale2) {
+  const int hkv = blockIdx.x / n_rt;
+  const int rt = blockIdx.x - hkv * n_rt;
+  const int lpage = blockIdx.y;
+  const int b = blockIdx.z;
+  const int lane = threadIdx.x;
+  const int low = lane & 31;
+  const int hi = lane >> 5;
+
+  const long pos_raw = pos_dev[b];
+  if (pos_raw < 0) return;
+  const int top = max_pages * V6_BN - 1;
+  const int p0 = pos_raw > top ? top : (int)pos_raw;
+  const int nq = attn_clampi(nq_dev[b], 1, T);
+  const int last = min(p0 + nq - 1, top);        // the slot's last valid row
+  const int kv0 = lpage * V6_BN;
+  if (kv0 > last) return;
+  const int n_valid = G * nq;
+  const int r0 = rt * AVF_ROWS;
+  if (r0 >= n_valid) return;
+  const int rlast = min(r0 + AVF_ROWS - 1, n_valid - 1);
+  if (kv0 > min(p0 + rlast / G, top)) return;    // page beyond every row
+
+  const int rr = r0 + low;
+  const int reff = min(rr, n_valid - 1);
+  const int t = reff / G;
+  const int h = hkv * G + (reff - t * G);
+  const int qrow = min(p0 + t, top);             // cache position
+
+  const int page = attn_clampi(table[(long)b * max_pages + lpage], 0,
+                               n_pages - 1);
+  const long pbase = ((long)page * n_kv + hkv) * (V6_BN * ATTN_D);
+  const u16* kp = kpool + pbase;
+  const u16* vp = vpool + pbase;
+
+  __shared__ __attribute__((aligned(16))) u16 vt[V6_V_U16];
+  char* vtb = reinterpret_cast<char*>(vt);
+
+  AttnFrag qf[8], k0[8], k1[8];
+  attn_load_row(qf, q + (((long)b * T + t) * n_heads + h) * ATTN_D, hi);
+  attn_load_row(k0, kp + low * ATTN_D, hi);
+  attn_load_row(k1, kp + (32 + low) * ATTN_D, hi);
+
+  // V: the wave plays thread groups i = 0..7 of attn_write_t (rows 8i ..
+  // 8i+7); rows beyond the slot's last valid one go in as zeros
+  const int vr = (lane >> 4) * 2;
+  const int vc = (lane & 15) * 8;
+  const int nrow = last - kv0 + 1;               // >= 1 valid rows of the page
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = i * 8 + vr;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    uint4 a = *reinterpret_cast<const uint4*>(vp + row * ATTN_D + vc);
+    uint4 c = *reinterpret_cast<const uint4*>(vp + (row + 1) * ATTN_D + vc);
+    if (row >= nrow) a = z;
+    if (row + 1 >= nrow) c = z;
+    attn_write_t(vtb, a, c, lane + 64 * i);
+  }
+
+  f32x16 s0, s1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+#pragma unroll
+  for (int kc = 0; kc < 8; ++kc) {
+    s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0[kc].v, qf[kc].v, s0,
+                                                 0, 0, 0);
+    s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1[kc].v, qf[kc].v, s1,
+                                                 0, 0, 0);
+  }
+  float pm = -1e30f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+    float x0 = s0[r] * scale2;
+    if (kvr > qrow) x0 = -1e30f;
+    s0[r] = x0;
+    float x1 = s1[r] * scale2;
+    if (kvr + 32 > qrow) x1 = -1e30f;
+    s1[r] = x1;
+    pm = fmaxf(pm, fmaxf(x0, x1));
+  }
+  pm = fmaxf(pm, __shfl_xor(pm, 32, 64));
+  float psum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float e0 = exp2_raw(s0[r] - pm);
+    const float e1 = exp2_raw(s1[r] - pm);
+    s0[r] = e0;
+    s1[r] = e1;
+    psum += e0 + e1;
+  }
+  psum += __shfl_xor(psum, 32, 64);
+  AttnFrag pa[4];
+#pragma unroll
+  for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc)
+      pa[sub * 2 + cc].v = attn_repack(sub == 0 ? s0 : s1, cc * 8);
+
+  __syncthreads();                               // the V^T image has landed
+  f32x16 oacc[4];
+  attn_zero(oacc);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) {
+      bf16x8 vf = *reinterpret_cast<const bf16x8*>(
+          &vtb[vt_byte(ds * 32 + low, c * 16 + hi * 8)]);
+      oacc[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pa[c].v,
+                                                         oacc[ds], 0, 0, 0);
+    }
+  }
+
+  if (rr < n_valid && kv0 <= qrow) {
+    float* rec = ws + ((((long)b * n_kv + hkv) * max_pages + lpage)
+                       * ((long)G * T) + rr) * AVF_REC;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) attn_store_f32(rec, oacc[ds], ds, hi);
+    if (hi == 0) {
+      float2 ml;
+      ml.x = pm;
+      ml.y = psum;
+      *reinterpret_cast<float2*>(rec + ATTN_D) = ml;
+    }
+  }
+}
+
+// grid (B * T * H), 128 threads <-> d: merge the pages of one (b, t, head)
+ATTN_NO_PK_F32 __global__ __launch_bounds__(128)
+void attn_verify_combine_kernel(
+    const float* __restrict__ ws, u16* __restrict__ o,
+    const long* __restrict__ pos_dev, const int* __restrict__ nq_dev,
+    int T, int n_heads, int G, int n_kv, int max_pages) {
+  const int h = blockIdx.x % n_heads;
+  const int bt = blockIdx.x / n_heads;
+  const int t = bt % T;
+  const int b = bt / T;
+  const int tid = threadIdx.x;
+  u16* orow = o + (long)blockIdx.x * ATTN_D;
+  const long pos_raw = pos_dev[b];
+  if (pos_raw < 0 || t >= attn_clampi(nq_dev[b], 1, T)) {
+    orow[tid] = 0;
+    return;
+  }
+  const int top = max_pages * V6_BN - 1;
+  const int p0 = pos_raw > top ? top : (int)pos_raw;
+  const int n_merge = min(p0 + t, top) / V6_BN + 1;        // <= max_pages
+  const int hkv = h / G;
+  const long rows = (long)G * T;
+  const long step = rows * AVF_REC;                        // page to page
+  const float* base = ws + (((long)b * n_kv + hkv) * max_pages * rows
+                            + (t * G + (h - hkv * G))) * AVF_REC;
+  float M = -1e30f;
+  for (int c = 0; c < n_merge; ++c) M = fmaxf(M, base[c * step + ATTN_D]);
+  float L = 0.f, od = 0.f;
+  for (int c = 0; c < n_merge; ++c) {
+    const float* pc = base + c * step;
+    const float w = exp2_raw(pc[ATTN_D] - M);
+    L += w * pc[ATTN_D + 1];
+    od += w * pc[tid];
+  }
+  orow[tid] = attn_f2bf(od / fmaxf(L, 1e-30f));
+}
+
+// ===========================================================================
 // v6 flash-attention BACKWARD (causal, bf16, D=128, GQA).
 //
 // Standard flash backward split into two walks plus a delta precompute:
@@ -2768,6 +2999,40 @@ extern "C" int attn_prefill_paged(void* stream, const void* q,
                      (const int*)block_table, (const int*)work, n_heads,
                      n_heads / n_kv_heads, n_kv_heads, T, B, n_pages,
                      max_pages, scale * ATTN_LOG2E);
+  return 0;
+}
+
+// paged speculative verify (attn_verify_partial_kernel + combine): q/o
+// [B, T, H, 128] bf16 with 1 <= T <= 8, pools [n_pages, n_kv, 64, 128] bf16
+// contiguous, block_table [B, max_pages] int32, pos [B] int64 (position of
+// the slot's first token, negative = idle), n_q [B] int32, ws fp32
+// [B, n_kv, max_pages, G*T, 132] scratch. No host-side input.
+extern "C" int attn_verify_paged(void* stream, const void* q,
+                                 const void* k_pool, const void* v_pool,
+                                 const void* block_table, const void* pos,
+                                 const void* n_q, void* ws, void* o, int B,
+                                 int T, int n_heads, int n_kv_heads,
+                                 int n_pages, int max_pages, float scale) {
+  if (B <= 0 || B > 65535 || T < 1 || T > 8 || n_heads <= 0 ||
+      n_kv_heads <= 0 || n_heads % n_kv_heads != 0 || n_pages <= 0 ||
+      max_pages <= 0 || max_pages > 65535 || !block_table || !pos || !n_q ||
+      !ws || (long)B * T * n_heads > 0x7fffffffL)
+    return -1;
+  const int G = n_heads / n_kv_heads;
+  const int n_rt = (G * T + AVF_ROWS - 1) / AVF_ROWS;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(attn_verify_partial_kernel,
+                     dim3((unsigned)(n_kv_heads * n_rt), (unsigned)max_pages,
+                          (unsigned)B),
+                     dim3(64), 0, st, (const u16*)q, (const u16*)k_pool,
+                     (const u16*)v_pool, (const long*)pos, (const int*)n_q,
+                     (const int*)block_table, (float*)ws, T, n_heads, G,
+                     n_kv_heads, n_rt, n_pages, max_pages,
+                     scale * ATTN_LOG2E);
+  hipLaunchKernelGGL(attn_verify_combine_kernel,
+                     dim3((unsigned)(B * T * n_heads)), dim3(128), 0, st,
+                     (const float*)ws, (u16*)o, (const long*)pos,
+                     (const int*)n_q, T, n_heads, G, n_kv_heads, max_pages);
   return 0;
 }
 

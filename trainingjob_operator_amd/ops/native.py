@@ -94,6 +94,11 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # n_blocks, T, H, n_kv, B, n_pages, max_pages, scale)
     _sig(lib.attn_prefill_paged, [vp, vp, vp, vp, vp, vp, vp,
                                   i, i, i, i, i, i, i, f], i)
+    # paged speculative verify: (q [B,T,H,128], k_pool, v_pool, block_table,
+    # pos int64 [B], n_q int32 [B], ws, o, B, T, H, n_kv, n_pages,
+    # max_pages, scale)
+    _sig(lib.attn_verify_paged, [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                 i, i, i, i, i, i, f], i)
     # clamp of one work row (host callable): (io int[4], T, B, max_pages)
     _sig(lib.attn_prefill_work_decode, [ctypes.POINTER(ctypes.c_int),
                                         i, i, i], i)

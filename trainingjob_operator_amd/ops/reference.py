@@ -115,6 +115,42 @@ def decode_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
     return o.reshape(B, H, 1, D).to(q.dtype)
 
 
+def verify_attention_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, block_table: torch.Tensor,
+                           pos: torch.Tensor, n_q: torch.Tensor,
+                           scale: float) -> torch.Tensor:
+    """Twin of attn_verify_paged: q [B,T,H,D]; token t of slot b sits at
+    cache position pos[b] + t and attends rows 0..pos[b]+t of the slot's
+    pages. fp32 math, any head_dim, result in q.dtype. Rows of an idle
+    slot (pos[b] < 0) and rows t >= n_q[b] (n_q clamped into 1..T) come
+    out as zeros; cache rows beyond a token's position are never used,
+    whatever they hold."""
+    B, T, H, D = q.shape
+    n_kv = k_pool.shape[1]
+    G = H // n_kv
+    dev = q.device
+    k = _paged_gather(k_pool, block_table).float()
+    v = _paged_gather(v_pool, block_table).float()
+    L = k.shape[2]
+    pos = pos.to(dev)
+    qpos = (pos.clamp(0, L - 1)[:, None]
+            + torch.arange(T, device=dev)[None, :]).clamp(max=L - 1)  # [B,T]
+    live = ((pos >= 0)[:, None]
+            & (torch.arange(T, device=dev)[None, :]
+               < n_q.to(dev).long().clamp(1, T)[:, None]))            # [B,T]
+    seen = torch.arange(L, device=dev)[None, None, :] <= qpos[:, :, None]
+    used = (seen & live[:, :, None]).any(dim=1)[:, None, :, None]  # [B,1,L,1]
+    k = torch.where(used, k, torch.zeros_like(k))
+    v = torch.where(used, v, torch.zeros_like(v))
+    s = torch.einsum("btkgd,bksd->btkgs",
+                     q.reshape(B, T, n_kv, G, D).float(), k) * scale
+    s = s.masked_fill(~seen[:, :, None, None, :], float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    o = torch.einsum("btkgs,bksd->btkgd", p, v)
+    o = torch.where(live[:, :, None, None, None], o, torch.zeros_like(o))
+    return o.reshape(B, T, H, D).to(q.dtype)
+
+
 def rope_cache_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
                      v_pool: torch.Tensor, inv_freq: torch.Tensor,
                      block_table: torch.Tensor, pos: torch.Tensor,
