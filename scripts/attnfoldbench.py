@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""dv + dk time by strip ownership (AITJ_ATTN_BWD_FOLD 0 | 1 | 2).
+"""dv + dk time by strip ownership (AITJ_ATTN_BWD_FOLD 0 | 1 | 2 | 3).
 
 Run it under the profiler, then read the trace back:
 
@@ -15,7 +15,8 @@ switches them through its environment. It prints the cell list. `read`
 takes the i-th dv and the i-th dk dispatch of the kernel trace (whatever
 the kernel is called under that ownership) as call i of that list and
 prints one JSON line per cell: average and standard deviation, us, over
-the timed calls."""
+the timed calls. Under 3 (fused) one kernel writes both gradients: its time
+is the cell's `sum`, and `dv` and `dk` stay 0."""
 import csv
 import glob
 import json
@@ -34,7 +35,7 @@ def cells():
     out = []
     for rep in range(REPS):
         for B in (1, 2, 4, 8):
-            for fold in ("0", "1", "2"):
+            for fold in ("0", "1", "2", "3"):
                 out.append(dict(rep=rep, B=B, split="0", fold=fold))
             if B <= 2:
                 out.append(dict(rep=rep, B=B, split="1", fold="0"))
@@ -68,25 +69,31 @@ def read(outdir):
     rows = list(csv.DictReader(open(paths[0])))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     per = {}
-    for tag in ("attn_bwd_dv", "attn_bwd_dk", "attn_bwd_reduce"):
-        per[tag] = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-                    for r in rows if tag in r["Kernel_Name"]]
+    for tag in ("attn_bwd_dv", "attn_bwd_dk", "attn_bwd_dkdv",
+                "attn_bwd_reduce"):
+        per[tag] = iter([
+            (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+            for r in rows if tag + "_" in r["Kernel_Name"]])
     n = WARM + TIMED
-    cs = cells()
-    assert len(per["attn_bwd_dv"]) == len(per["attn_bwd_dk"]) == n * len(cs)
-    red = iter(per["attn_bwd_reduce"])
-    for i, cell in enumerate(cs):
-        res = dict(cell)
-        for tag in ("attn_bwd_dv", "attn_bwd_dk"):
-            t = per[tag][i * n + WARM:(i + 1) * n]
-            res[tag[-2:]] = round(statistics.mean(t), 1)
-            res[tag[-2:] + "_sd"] = round(statistics.stdev(t), 1)
-        res["reduce"] = 0.0
-        if cell["split"] == "1":
-            t = [next(red) for _ in range(n)][WARM:]
-            res["reduce"] = round(statistics.mean(t), 1)
-        res["sum"] = round(res["dv"] + res["dk"] + res["reduce"], 1)
+    for cell in cells():
+        res = dict(cell, dv=0.0, dk=0.0, reduce=0.0)
+        if cell["fold"] == "3":
+            tags = ("attn_bwd_dkdv",)
+        elif cell["split"] == "1":
+            tags = ("attn_bwd_dv", "attn_bwd_dk", "attn_bwd_reduce")
+        else:
+            tags = ("attn_bwd_dv", "attn_bwd_dk")
+        total = 0.0
+        for tag in tags:
+            t = [next(per[tag]) for _ in range(n)][WARM:]
+            key = tag[len("attn_bwd_"):]
+            res[key] = round(statistics.mean(t), 1)
+            res[key + "_sd"] = round(statistics.stdev(t), 1)
+            total += res[key]
+        res["sum"] = round(total, 1)
         print(json.dumps(res))
+    for tag, left in per.items():
+        assert next(left, None) is None, f"{tag} dispatches left over"
 
 
 if __name__ == "__main__":

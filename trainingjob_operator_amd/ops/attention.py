@@ -84,6 +84,15 @@ does), above that both keep the identity. `lib.attn_bwd_pair_decode` is
 the host copy of the ownership function and `lib.attn_bwd_fold_mode` says
 which ownership a launch of a given shape gets.
 
+Fused dK/dV (`attn_bwd_dkdv_pair_kernel`, AITJ_ATTN_BWD_FOLD=3): the dk
+pair walk computes the P the dv walk computes again, so one kernel keeps P
+next to dS, swaps both between the partner waves and accumulates dv and
+then dk over the same chunks in the same order: one staging, one exp pass,
+one launch, bits kept. Causal unsplit launches only, like 2. Since it
+exists the unset rule above reads: an unsplit causal launch of up to four
+workgroups per CU is fused (`attn_bwd_fold_mode` says 3 for both kernels),
+a larger one keeps the identity (profiles/r16_dkdv_fused.md).
+
 Document-masked attention (`flash_attention_docs`, `packed_rope_attention(
 ..., doc_bounds=)`; layouts in ops/docmask.py): a window that holds several
 documents attends causally inside each one. The layout is one int32 tensor

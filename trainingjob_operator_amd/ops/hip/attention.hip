@@ -2721,6 +2721,254 @@ __global__ __launch_bounds__(512) void attn_bwd_dk_pair_kernel(
 #undef BK_WRITE_QT
 
 // ---------------------------------------------------------------------------
+// dK and dV in ONE pair walk (causal, unsplit): the grid, attn_sched_block,
+// attn_bwd_pair ownership, two phases and head loop of
+// attn_bwd_dk_pair_kernel, which already computes the P that
+// attn_bwd_dv_pair_kernel computes again (same x = s*scale2 - lse2, same mask
+// test, same exp2_raw). Per tile an active wave keeps P next to dS, repacks
+// both, swaps both with its partner, accumulates dvacc[j] over chunks 0..3
+// ascending against the dO^T image and then dkacc[j] against the Q^T image:
+// every accumulator meets the fragments of the two pair kernels in their
+// order, so dk and dv keep their bits.
+//
+// Staging, by all 512 threads: the Q and dO row images of the next tile by
+// glds into the other buffer, as in the dk walks. The two transposed images
+// are not staged through registers (BK_WRITE_QT / BV_WRITE_DOT: a second
+// global read of each row and 16 VGPRs held across the S phase, which this
+// kernel does not have) but built by attn_transpose from the landed row
+// images of the current tile, as dq builds K^T. The bytes of an image are
+// the same either way.
+//
+// LDS: two buffers of (Q rows, dO rows, lse, delta) = 2 x 33,280 B, one Q^T
+// and one dO^T image (2 x 18,688 B) and two exchange areas, P and dS (2 x
+// 16,384 B): 136,704 B. One exchange area used for P and then for dS would
+// need a barrier between a wave's read of P and its partner's write of dS,
+// on top of the one before the dS read.
+//
+// Barriers: every wave reaches, per phase and q head, one barrier after the
+// first staging and two per tile, as in the pair kernels: X (both images of
+// this tile and the P and dS fragments of both subs written) and the
+// end-of-tile one (images and exchange areas read; rows of the next tile
+// landed). All stand outside `if (active)` and `if (have_next)`; qt0, qtn
+// and the head range are workgroup-uniform, so the eight waves count
+// gqa * (1 + 2 * (qtn - qt0)) per phase on every path. Partners share kv0w,
+// hence `active`. Images and exchange areas are written only between an
+// end-of-tile (or first-staging) barrier and X and read only between X and
+// the end-of-tile barrier; a row buffer is read in the tile after the
+// barrier its glds landed before, and refilled one tile later.
+// ---------------------------------------------------------------------------
+
+#define BF_ROWS_U16 (2 * V6_BN * ATTN_D)            // Q rows, then dO rows
+#define BF_BUF_U16 (BF_ROWS_U16 + 128 + 128)        // + lse, delta (64 f32)
+#define BF_T_U16 (ATTN_D * (VT_PITCH_B / 2) + 128)  // one transposed image
+
+// the two d subtiles ds0, ds0 + 1 of a wave's strip rows, rounded to bf16
+__device__ __forceinline__ void attn_pair_store(u16* row,
+                                                const f32x16 (&acc)[2],
+                                                int ds0, int hi) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int d0 = 8 * g + 4 * hi + 32 * (ds0 + j);
+      uint2 wv;
+      wv.x = cvt_pk_bf16(acc[j][4 * g + 0], acc[j][4 * g + 1]);
+      wv.y = cvt_pk_bf16(acc[j][4 * g + 2], acc[j][4 * g + 3]);
+      *reinterpret_cast<uint2*>(row + d0) = wv;
+    }
+  }
+}
+
+__global__ __launch_bounds__(512) void attn_bwd_dkdv_pair_kernel(
+    const u16* __restrict__ q, const u16* __restrict__ k,
+    const u16* __restrict__ v, const u16* __restrict__ dout,
+    const float* __restrict__ lse, const float* __restrict__ delta,
+    u16* __restrict__ dk, u16* __restrict__ dv,
+    long q_sb, long q_sh, long q_ss,
+    long k_sb, long k_sh, long k_ss,
+    long v_sb, long v_sh, long v_ss,
+    long do_sb, long do_sh, long do_ss,
+    long dk_sb, long dk_sh, long dk_ss,
+    long dv_sb, long dv_sh, long dv_ss,
+    int n_heads, int n_kv_heads, int S, float scale, int batch, int sched) {
+  const int nrb = S / 256;
+  const AttnBlock blk = attn_sched_block(blockIdx.x, nrb, n_kv_heads, batch,
+                                         sched);
+  const int gqa_group = n_heads / n_kv_heads;
+  const int hkv = blk.head;
+  const int b = blk.batch;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int low = lane & 31;
+  const int hi = lane >> 5;
+  const float scale2 = scale * ATTN_LOG2E;
+
+  __shared__ __attribute__((aligned(16))) u16 lds[2][BF_BUF_U16];
+  __shared__ __attribute__((aligned(16))) u16 timg[2][BF_T_U16];
+  __shared__ __attribute__((aligned(16))) uint4 xch[2 * ATTN_PAIR_XCH_U4];
+  char* qtb = reinterpret_cast<char*>(&timg[0][0]);      // Q^T image
+  char* dotb = reinterpret_cast<char*>(&timg[1][0]);     // dO^T image
+  const int DOOFF = V6_BN * ATTN_D * 2;
+  const int LSEOFF = BF_ROWS_U16 * 2;
+  const int DLTOFF = LSEOFF + 256;
+  const int XDS = ATTN_PAIR_XCH_U4;          // the dS area follows the P area
+
+  const int qtn = S / 64;
+  const int wu64 = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+#pragma unroll 1
+  for (int phase = 0; phase < 2; ++phase) {
+    const AttnPair pr = attn_bwd_pair(blk.rank, phase, wu64, nrb);
+    const int kv0w = pr.kv0w;
+    const int kvrow = kv0w + low;
+    const int sub = pr.sub;
+    const int aoff = pr.ds0 * 32 * VT_PITCH_B;
+
+    const u16* kptr =
+        k + (long)b * k_sb + (long)hkv * k_sh + (long)kvrow * k_ss;
+    const u16* vptr =
+        v + (long)b * v_sb + (long)hkv * v_sh + (long)kvrow * v_ss;
+    AttnFrag kf[8], vf[8];
+#pragma unroll
+    for (int kc = 0; kc < 8; ++kc) {
+      kf[kc].u = *reinterpret_cast<const uint4*>(kptr + kc * 16 + hi * 8);
+      vf[kc].u = *reinterpret_cast<const uint4*>(vptr + kc * 16 + hi * 8);
+    }
+
+    f32x16 dkacc[2], dvacc[2];
+    attn_zero(dkacc);
+    attn_zero(dvacc);
+
+    const int qt0 = pr.qt0;
+
+    for (int g = 0; g < gqa_group; ++g) {
+      const int h = hkv * gqa_group + g;
+      const u16* qbase = q + (long)b * q_sb + (long)h * q_sh;
+      const u16* dobase = dout + (long)b * do_sb + (long)h * do_sh;
+      const float* lbase = lse + ((long)b * n_heads + h) * S;
+      const float* dbase = delta + ((long)b * n_heads + h) * S;
+
+      const u16* qgp[2];
+      const u16* dgp[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        qgp[i] = attn_glds_src(qbase, qt0 * 64, (i * 512 + tid) * 16, q_ss);
+        dgp[i] = attn_glds_src(dobase, qt0 * 64, (i * 512 + tid) * 16, do_ss);
+      }
+      const long qstep = (long)64 * q_ss;
+      const long dostep = (long)64 * do_ss;
+
+      // rows, lse and delta of tile QT into buffer BUFI
+      auto stage_in = [&](int bufi, int qt) {
+        attn_glds_rows2<512 * 8>(&lds[bufi][0], qgp, qstep,
+                                 &lds[bufi][DOOFF / 2], dgp, dostep,
+                                 wu64 * 64 * 8);
+        if (tid < 64)
+          *reinterpret_cast<float*>(&lds[bufi][LSEOFF / 2 + tid * 2]) =
+              lbase[qt * 64 + tid] * ATTN_LOG2E;
+        else if (tid < 128)
+          *reinterpret_cast<float*>(
+              &lds[bufi][DLTOFF / 2 + (tid - 64) * 2]) =
+              dbase[qt * 64 + tid - 64];
+      };
+
+      stage_in(0, qt0);
+      __syncthreads();
+
+      int cur = 0;
+      for (int qt = qt0; qt < qtn; ++qt) {
+        const bool have_next = (qt + 1) < qtn;
+        if (have_next) stage_in(cur ^ 1, qt + 1);
+
+        const u16* rows = &lds[cur][0];
+        const char* qb_ = reinterpret_cast<const char*>(rows);
+        const char* dob = qb_ + DOOFF;
+        const float* lse2t = reinterpret_cast<const float*>(qb_ + LSEOFF);
+        const float* dltt = reinterpret_cast<const float*>(qb_ + DLTOFF);
+        const bool active = qt * 64 + 63 >= kv0w;
+        const bool need_mask = qt * 64 < kv0w + 32;
+
+        attn_transpose(rows, qtb, tid);
+        attn_transpose(rows + DOOFF / 2, dotb, tid);
+
+        if (active) {
+          f32x16 s, dp;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+          for (int kc = 0; kc < 8; ++kc) {
+            bf16x8 a = *reinterpret_cast<const bf16x8*>(
+                &qb_[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kc].v, s,
+                                                        0, 0, 0);
+            bf16x8 a2 = *reinterpret_cast<const bf16x8*>(
+                &dob[k_byte(sub * 32 + low, kc * 16 + hi * 8)]);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, vf[kc].v, dp,
+                                                         0, 0, 0);
+          }
+          // s becomes P, dp becomes dS
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int qr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            float x = s[r] * scale2 - lse2t[sub * 32 + qr];
+            if (need_mask && qt * 64 + sub * 32 + qr < kvrow) x = -1e30f;
+            const float p = exp2_raw(x);
+            s[r] = p;
+            dp[r] = p * (dp[r] - dltt[sub * 32 + qr]) * scale;
+          }
+#pragma unroll
+          for (int cc = 0; cc < 2; ++cc) {
+            AttnFrag f;
+            f.v = attn_repack(s, cc * 8);
+            xch[attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.u;
+            f.v = attn_repack(dp, cc * 8);
+            xch[XDS + attn_pair_xch(wu64, sub * 2 + cc) + lane] = f.u;
+          }
+        }
+        v7_barrier();                        // X: images and fragments written
+        if (active) {
+          // dV^T += dO^T @ P over 4 q chunks x this wave's 2 d subtiles
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            AttnFrag pf;
+            pf.u = xch[attn_pair_xch(wu64, c) + lane];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              bf16x8 af = *reinterpret_cast<const bf16x8*>(
+                  &dotb[aoff + vt_byte(j * 32 + low, c * 16 + hi * 8)]);
+              dvacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  af, pf.v, dvacc[j], 0, 0, 0);
+            }
+          }
+          // dK^T += Q^T @ dS, the same chunks and subtiles
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            AttnFrag pf;
+            pf.u = xch[XDS + attn_pair_xch(wu64, c) + lane];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              bf16x8 af = *reinterpret_cast<const bf16x8*>(
+                  &qtb[aoff + vt_byte(j * 32 + low, c * 16 + hi * 8)]);
+              dkacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  af, pf.v, dkacc[j], 0, 0, 0);
+            }
+          }
+        }
+        __syncthreads();
+        cur ^= 1;
+      }
+    }
+
+    attn_pair_store(
+        dk + (long)b * dk_sb + (long)hkv * dk_sh + (long)kvrow * dk_ss,
+        dkacc, pr.ds0, hi);
+    attn_pair_store(
+        dv + (long)b * dv_sb + (long)hkv * dv_sh + (long)kvrow * dv_ss,
+        dvacc, pr.ds0, hi);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Split dK/dV: sum the gqa_group fp32 partials of each kv head in fixed
 // order ((p0 + p1) + p2) + ..., round once to bf16 (the same
 // v_cvt_pk_bf16_f32 the unsplit epilogue uses) and write dk and dv through
@@ -3148,6 +3396,19 @@ static bool attn_bwd_use_split(int batch, int n_heads, int n_kv_heads, int S,
 // carry the second barrier, and the pair reads 7 us behind the fold there
 // and 11 us behind it in the step trace. So unset gives dk the pair and dv
 // the fold.
+//
+// FUSED (AITJ_ATTN_BWD_FOLD=3, causal and unsplit like 2) is the pair
+// ownership with dv and dk in one walk, attn_bwd_dkdv_pair_kernel; both
+// kernels get the answer or neither does. One walk instead of two beats
+// every other ownership at every grid measured, the identity's backfill
+// included. Unsplit, us, dv + dk: identity / fold / dv fold + dk pair /
+// fused, two runs averaged (profiles/r16_dkdv_fused.md):
+//   B=1 1330 / 1144 / 1005 /  687    B=2 1429 / 1200 / 1041 /  713
+//   B=4 1706 / 2133 / 2104 / 1499    B=8 3456 / 4441 / 4419 / 3049
+// So unset, an unsplit causal launch is fused up to four workgroups per CU,
+// the largest grid measured; above that it keeps the identity.
+#define ATTN_STRIPS_FUSED 3
+#define ATTN_FUSED_MAX_WGS (4 * ATTN_NUM_CUS)
 #define ATTN_BWD_DV 0
 #define ATTN_BWD_DK 1
 static int attn_bwd_use_fold(int batch, int n_heads, int n_kv_heads, int S,
@@ -3157,14 +3418,45 @@ static int attn_bwd_use_fold(int batch, int n_heads, int n_kv_heads, int S,
   if (e && std::strcmp(e, "0") == 0) return ATTN_STRIPS_IDENTITY;
   if (e && std::strcmp(e, "1") == 0) return ATTN_STRIPS_FOLD;
   if (e && std::strcmp(e, "2") == 0 && !split) return ATTN_STRIPS_PAIR;
+  if (e && std::strcmp(e, "3") == 0 && !split) return ATTN_STRIPS_FUSED;
   const long wgs = (long)batch * (split ? n_heads : n_kv_heads) * (S / 256);
-  if (wgs > ATTN_NUM_CUS) return ATTN_STRIPS_IDENTITY;
-  if (split || kernel != ATTN_BWD_DK) return ATTN_STRIPS_FOLD;
-  return ATTN_STRIPS_PAIR;
+  if (!split)
+    return wgs <= ATTN_FUSED_MAX_WGS ? ATTN_STRIPS_FUSED
+                                     : ATTN_STRIPS_IDENTITY;
+  return wgs > ATTN_NUM_CUS ? ATTN_STRIPS_IDENTITY : ATTN_STRIPS_FOLD;
+}
+
+// What one of the two kernels runs alone where the launch would be fused
+// (the per-kernel timing entry): the rule from before the fusion.
+static inline int attn_bwd_unfused(int fold, int kernel) {
+  if (fold != ATTN_STRIPS_FUSED) return fold;
+  return kernel == ATTN_BWD_DK ? ATTN_STRIPS_PAIR : ATTN_STRIPS_FOLD;
+}
+
+// dv and dk of a causal unsplit launch in one walk (ATTN_STRIPS_FUSED)
+static void launch_bwd_dkdv_fused(hipStream_t st, const void* q,
+                                  const void* k, const void* v,
+                                  const void* dout, const void* lse,
+                                  const void* delta, void* dk, void* dv,
+                                  AttnStride qs, AttnStride ks, AttnStride vs,
+                                  AttnStride dos, AttnStride dks,
+                                  AttnStride dvs, int batch, int n_heads,
+                                  int n_kv_heads, int S, float scale,
+                                  int sched) {
+  hipLaunchKernelGGL(attn_bwd_dkdv_pair_kernel,
+                     dim3((S / 256) * n_kv_heads * batch), dim3(512), 0, st,
+                     (const u16*)q, (const u16*)k, (const u16*)v,
+                     (const u16*)dout, (const float*)lse,
+                     (const float*)delta, (u16*)dk, (u16*)dv,
+                     qs.sb, qs.sh, qs.ss, ks.sb, ks.sh, ks.ss,
+                     vs.sb, vs.sh, vs.ss, dos.sb, dos.sh, dos.ss,
+                     dks.sb, dks.sh, dks.ss, dvs.sb, dvs.sh, dvs.ss,
+                     n_heads, n_kv_heads, S, scale, batch, sched);
 }
 
 // The ownership a launch of this shape gets right now (0 identity, 1 fold,
-// 2 pair), for kernel 0 = dv, 1 = dk. Host only.
+// 2 pair, 3 fused: one kernel for both), for kernel 0 = dv, 1 = dk. Host
+// only.
 extern "C" int attn_bwd_fold_mode(int batch, int n_heads, int n_kv_heads,
                                   int S, int causal, int split, int kernel) {
   return attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, causal != 0,
@@ -3271,6 +3563,12 @@ static void launch_bwd_core(hipStream_t st, const void* q, const void* k,
   const int fold_k = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S_kv,
                                        CAUSAL, split, ATTN_BWD_DK);
   dim3 grid(nrb * (split ? n_heads : n_kv_heads) * batch), block(512);
+  if (fold_k == ATTN_STRIPS_FUSED) {         // causal and unsplit only
+    launch_bwd_dkdv_fused(st, q, k, v, dout, lse, delta, dk, dv, qs, ks, vs,
+                          dos, dks, dvs, batch, n_heads, n_kv_heads, S, scale,
+                          sched);
+    return;
+  }
   if (fold_v == ATTN_STRIPS_PAIR) {          // causal and unsplit only
     hipLaunchKernelGGL(attn_bwd_dv_pair_kernel, grid, block, 0, st,
                        (const u16*)q, (const u16*)k, (const u16*)dout,
@@ -3798,17 +4096,21 @@ extern "C" int attn_doc_bwd_strided(void* stream, const void* q,
 }
 
 // One backward kernel alone, for per-kernel timing (scripts/
-// attndocbench.py): part 1 dq, 2 dv, 4 dk. lse and delta are inputs. With
-// bounds the document kernel; with null bounds the causal unsplit launch,
-// dv/dk under the ownership the causal entries would pick for the shape
-// now. st: 8 triples as in attn_bwd_strided (out unused).
+// attndocbench.py): part 1 dq, 2 dv, 4 dk, or 6 for dv and dk as the
+// training entries launch them (one fused kernel where the rule fuses). lse
+// and delta are inputs. With bounds the document kernel; with null bounds
+// the causal unsplit launch, dv/dk under the ownership the causal entries
+// would pick for the shape now (a kernel asked for alone where they would
+// fuse: attn_bwd_unfused). st: 8 triples as in attn_bwd_strided (out unused).
 extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
                              const void* v, const void* dout,
                              const void* lse, const void* delta, void* dq,
                              void* dk, void* dv, const int* bounds,
                              const long* st, int batch, int n_heads,
                              int n_kv_heads, int S, float scale, int part) {
-  if (part != ATTN_PART_DQ && part != ATTN_PART_DV && part != ATTN_PART_DK)
+  const int dkdv = ATTN_PART_DV | ATTN_PART_DK;
+  if (part != ATTN_PART_DQ && part != ATTN_PART_DV && part != ATTN_PART_DK &&
+      part != dkdv)
     return -1;
   if (bounds)
     return launch_doc_bwd(stream, q, k, v, nullptr, dout, lse,
@@ -3836,9 +4138,20 @@ extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
                        ATTN_S3(ks), ATTN_S3(vs), ATTN_S3(dos), ATTN_S3(dqs),
                        n_heads, n_heads / n_kv_heads, S, scale, batch, sched,
                        S, bounds);
-  } else if (part == ATTN_PART_DV) {
-    const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true,
-                                       false, ATTN_BWD_DV);
+  }
+  const bool fused = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true,
+                                       false, ATTN_BWD_DK) ==
+                     ATTN_STRIPS_FUSED;
+  if (part == dkdv && fused) {
+    launch_bwd_dkdv_fused(hs, q, k, v, dout, lse, delta, dk, dv, qs, ks, vs,
+                          dos, dks, dvs, batch, n_heads, n_kv_heads, S, scale,
+                          sched);
+    return 0;
+  }
+  if (part & ATTN_PART_DV) {
+    const int fold = attn_bwd_unfused(
+        attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true, false,
+                          ATTN_BWD_DV), ATTN_BWD_DV);
     if (fold == ATTN_STRIPS_PAIR)
       hipLaunchKernelGGL(attn_bwd_dv_pair_kernel, grid, block, 0, hs,
                          (const u16*)q, (const u16*)k, (const u16*)dout,
@@ -3853,9 +4166,11 @@ extern "C" int attn_bwd_part(void* stream, const void* q, const void* k,
                          ATTN_S3(ks), ATTN_S3(dos), ATTN_S3(dvs), n_heads,
                          n_kv_heads, S, scale, (float*)nullptr, batch, sched,
                          fold, S, bounds);
-  } else {
-    const int fold = attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true,
-                                       false, ATTN_BWD_DK);
+  }
+  if (part & ATTN_PART_DK) {
+    const int fold = attn_bwd_unfused(
+        attn_bwd_use_fold(batch, n_heads, n_kv_heads, S, true, false,
+                          ATTN_BWD_DK), ATTN_BWD_DK);
     if (fold == ATTN_STRIPS_PAIR)
       hipLaunchKernelGGL(attn_bwd_dk_pair_kernel, grid, block, 0, hs,
                          (const u16*)q, (const u16*)k, (const u16*)v,
