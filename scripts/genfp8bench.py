@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""Decode tokens/s under the captured graph with fp8 and with bf16 decode
+weights, on one (quantised) model: two DecodeSessions alternate inside
+every round. Also checks once that the fp8 graph emits the eager fp8
+tokens.
+
+    genfp8bench.py [model] [batch ...] [--new N] [--rounds R]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("model", nargs="?", default="llama3-8b")
+    ap.add_argument("batch", nargs="*", type=int, default=[1, 8])
+    ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    from trainingjob_operator_amd.models.config import CONFIGS
+    from trainingjob_operator_amd.models.decode_graph import DecodeSession
+    from trainingjob_operator_amd.models.generate import (
+        build_inference_model, generate, quantize_decode_weights)
+    cfg = CONFIGS[args.model]
+    dev = torch.device("cuda:0")
+    model = build_inference_model(cfg, dev)
+    n = quantize_decode_weights(model)
+    print(f"{args.model}: {n} weights quantised", flush=True)
+    for batch in args.batch:
+        g = torch.Generator().manual_seed(batch)
+        prompt = torch.randint(0, cfg.vocab_size, (batch, args.prompt),
+                               generator=g).to(dev)
+        max_len = args.prompt + args.new + 8
+        ses = {w: DecodeSession(model, batch, max_len, weights=w)
+               for w in ("fp8", "bf16")}
+        outs = {w: s.generate(prompt, 8) for w, s in ses.items()}  # capture
+        eager = generate(model, prompt, max_new_tokens=8, weights="fp8")
+        agree = (outs["fp8"] == eager).float().mean().item()
+        print(f"b{batch}: fp8 graph against fp8 eager tokens: "
+              f"{agree:.0%} equal", flush=True)
+        tps = {w: [] for w in ses}
+        for _ in range(args.rounds):
+            for w, s in ses.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                s.generate(prompt, args.new)
+                torch.cuda.synchronize()
+                tps[w].append(batch * args.new / (time.perf_counter() - t0))
+        med = {w: statistics.median(v) for w, v in tps.items()}
+        for w, v in tps.items():
+            print(f"b{batch} {w}: {med[w]:.1f} tok/s incl. prefill (spread "
+                  f"{max(v) - min(v):.1f}, {batch * 1e3 / med[w]:.2f} "
+                  f"ms/token)")
+        print(f"b{batch} fp8 / bf16: {med['fp8'] / med['bf16']:.2f}x",
+              flush=True)
+        del ses
+
+
+if __name__ == "__main__":
+    main()

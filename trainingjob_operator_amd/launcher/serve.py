@@ -54,13 +54,15 @@ _PAGED_GAUGES = {}
 
 def create_app(model, model_name: str = "model", paged: bool = False,
                max_slots: int = 8, pool_pages: Optional[int] = None,
-               prefill_chunk: int = 0, lookup_k: int = 0):
+               prefill_chunk: int = 0, lookup_k: int = 0,
+               weights: str = "bf16"):
     """Build the FastAPI app around an already-constructed model (tests
     pass a CPU llama-tiny; the CLI builds the named config on cuda:0).
     paged=True serves /generate through a PagedEngine of `max_slots`
     sequences over `pool_pages` 64-row KV pages (default 32 per slot);
     prefill_chunk > 0 selects the engine's paged prefill with that many
-    prompt tokens per step, lookup_k > 0 its prompt-lookup speculation."""
+    prompt tokens per step, lookup_k > 0 its prompt-lookup speculation.
+    weights="fp8" decodes from e4m3 weights on every route."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -119,7 +121,7 @@ def create_app(model, model_name: str = "model", paged: bool = False,
         engine = PagedEngine(
             model, max_slots=max_slots, n_pages=pool_pages,
             graph=os.environ.get("AITJ_DECODE_GRAPH") == "1",
-            lookup_k=lookup_k,
+            lookup_k=lookup_k, weights=weights,
             **({"prefill": "paged", "prefill_chunk": int(prefill_chunk)}
                if prefill_chunk else {}))
         if mx:
@@ -174,7 +176,7 @@ def create_app(model, model_name: str = "model", paged: bool = False,
         if len(sessions) < 4:
             from ..models.decode_graph import DecodeSession
             max_len = max(need_len + 8, 2048)
-            ses = DecodeSession(model, batch, max_len)
+            ses = DecodeSession(model, batch, max_len, weights=weights)
             sessions[batch] = ses
             return ses
         return None                  # session pool full: eager path
@@ -275,7 +277,8 @@ def create_app(model, model_name: str = "model", paged: bool = False,
                 from ..models.generate import generate_lookup
                 out = generate_lookup(model, prompt, req.max_new_tokens,
                                       lookup_k=req.prompt_lookup,
-                                      eos_token=req.eos_token)
+                                      eos_token=req.eos_token,
+                                      weights=weights)
             elif ses is not None:
                 out = ses.generate(prompt, req.max_new_tokens,
                                    temperature=req.temperature,
@@ -286,7 +289,8 @@ def create_app(model, model_name: str = "model", paged: bool = False,
                                max_new_tokens=req.max_new_tokens,
                                temperature=req.temperature,
                                top_k=req.top_k,
-                               eos_token=req.eos_token, seed=req.seed)
+                               eos_token=req.eos_token, seed=req.seed,
+                               weights=weights)
             if device.type == "cuda":
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -336,6 +340,10 @@ def main(argv=None):
                     help="with --paged: prompt-lookup speculation, up to N "
                          "(<= 7) draft tokens per greedy request and step "
                          "(0 = plain decode)")
+    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: quantise the decode projections to e4m3 "
+                         "(per-row power-of-two scales) and stream those in "
+                         "every step of up to 16 rows")
     args = ap.parse_args(argv)
     if args.graph:
         os.environ["AITJ_DECODE_GRAPH"] = "1"
@@ -348,7 +356,7 @@ def main(argv=None):
     app = create_app(model, args.model, paged=args.paged,
                      max_slots=args.max_slots, pool_pages=args.pool_pages,
                      prefill_chunk=args.prefill_chunk,
-                     lookup_k=args.lookup_k)
+                     lookup_k=args.lookup_k, weights=args.weights)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 
 

@@ -28,13 +28,14 @@ from __future__ import annotations
 
 import torch
 
-from ..ops import decode_attention, decode_linear, fused_rmsnorm, native
-from .generate import KVCache, _layers_cached
+from ..ops import decode_attention, fused_rmsnorm, native
+from .generate import KVCache, _layers_cached, _proj, use_fp8_weights
 from .llama import LlamaModel
 
 
 def _step_static(model: LlamaModel, cur: torch.Tensor, cache: KVCache,
-                 pos_t: torch.Tensor, arange: torch.Tensor) -> torch.Tensor:
+                 pos_t: torch.Tensor, arange: torch.Tensor,
+                 fp8: bool = False) -> torch.Tensor:
     """One decode step with device-resident position: returns logits
     [B, V]. Every shape is independent of the position, so the whole
     call is stream-capturable."""
@@ -75,10 +76,11 @@ def _step_static(model: LlamaModel, cur: torch.Tensor, cache: KVCache,
             o = torch.einsum("bkgs,bksd->bkgd", p, vv.float())
         return o
 
-    x, residual = _layers_cached(model, model.embed(cur), attend)  # [B, 1, H]
+    x, residual = _layers_cached(model, model.embed(cur), attend,
+                                 fp8)                          # [B, 1, H]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
-    logits = decode_linear(normed, model.lm_head.weight)
+    logits = _proj(model.lm_head, normed, fp8)
     pos_t.add_(1)                                          # in-graph advance
     return logits.reshape(B, -1)
 
@@ -94,7 +96,9 @@ class GraphedDecoder:
     replays overwrite those same positions, so the cache stays correct.
     """
 
-    def __init__(self, model: LlamaModel, cache: KVCache, batch: int):
+    def __init__(self, model: LlamaModel, cache: KVCache, batch: int,
+                 fp8: bool = False):
+        self.fp8 = fp8
         dev = model.embed.weight.device
         self.model, self.cache = model, cache
         self.cur = torch.zeros(batch, dtype=torch.long, device=dev)
@@ -105,7 +109,7 @@ class GraphedDecoder:
 
     def _run(self) -> torch.Tensor:
         return _step_static(self.model, self.cur[:, None], self.cache,
-                            self.pos_t, self.arange)
+                            self.pos_t, self.arange, self.fp8)
 
     def prime(self) -> None:
         assert self.cache.len + 2 < self.cache.max_len, \
@@ -144,10 +148,15 @@ class DecodeSession:
     same cache buffers (stale rows beyond the fill are masked, never
     read) and resets `pos_t`. Per-request graph capture was ~15% of a
     512-token generation and dominates short requests.
+
+    weights="fp8" captures the step over the model's e4m3 decode weights
+    (generate.use_fp8_weights): half the bytes per token, same model.
     """
 
-    def __init__(self, model, batch: int, max_len: int):
+    def __init__(self, model, batch: int, max_len: int,
+                 weights: str = "bf16"):
         from .generate import KVCache
+        self.fp8 = use_fp8_weights(model, weights)
         self.model = model
         self.batch = batch
         self.max_len = max_len
@@ -168,9 +177,11 @@ class DecodeSession:
         self.model.eval()
         try:
             self.cache.len = 0                  # reuse buffers in place
-            last = _forward_cached(self.model, tokens, self.cache)[:, -1]
+            last = _forward_cached(self.model, tokens, self.cache,
+                                   self.fp8)[:, -1]
             if self.dec is None:
-                self.dec = GraphedDecoder(self.model, self.cache, B)
+                self.dec = GraphedDecoder(self.model, self.cache, B,
+                                          self.fp8)
                 self.dec.prime()                # captures ONCE
             else:
                 self.dec.pos_t.fill_(self.cache.len)

@@ -22,7 +22,9 @@ from typing import List, Optional
 
 import torch
 
-from ..ops import decode_linear, fused_rmsnorm, swiglu_packed
+from ..ops import (decode_linear, decode_linear_fp8, decode_swiglu,
+                   decode_swiglu_fp8, fused_rmsnorm, swiglu_packed)
+from ..ops.fp8_weight import quantize_rows
 from .config import LlamaConfig
 from .llama import LlamaModel, _sdpa
 
@@ -44,6 +46,75 @@ def build_inference_model(cfg, device):
     model.inv_freq = make_inv_freq(cfg.head_dim, cfg.rope_theta,
                                    device=device)
     return model.eval()
+
+
+def quantize_decode_weights(model) -> int:
+    """Quantise the decode projections to weight-only fp8, once: qkv_proj,
+    o_proj, gate_up_proj and down_proj of every dense block and the lm_head
+    get an `fp8_weight` (ops/fp8_weight.py) next to their own weight, and
+    that weight is overwritten with the dequantised values. The scales are
+    powers of two, so the write-back is exact in bf16: prefill, steps of
+    more than 16 rows and the bf16 GEMVs then compute the same model as the
+    fp8 GEMVs. The bf16 weights stay resident (this halves the bytes a
+    decode step streams, not the model's footprint). MoE experts, the
+    embedding (and an lm_head tied to it) and the norms are untouched, and
+    so is a weight whose shape the kernel does not take. An fp8_weight
+    remembers the version of the weight it was made from: after the weight
+    is written again (load_state_dict, an optimizer step) it is no longer
+    used, and the next call here replaces it. Returns the number of weights
+    that now carry one."""
+    mods = []
+    for blk in model.blocks:
+        mods += [(blk.attn.qkv_proj, False), (blk.attn.o_proj, False)]
+        if hasattr(blk, "mlp"):
+            mods += [(blk.mlp.gate_up_proj, True),
+                     (blk.mlp.down_proj, False)]
+    if model.lm_head.weight is not model.embed.weight:
+        mods.append((model.lm_head, False))
+    done = 0
+    with torch.no_grad():
+        for mod, gate_up in mods:
+            if _fp8_weight(mod) is None:
+                w8 = quantize_rows(mod.weight, gate_up=gate_up)
+                if w8 is None:
+                    continue
+                mod.weight.copy_(w8.dequant())
+                mod.fp8_weight = w8
+                mod.fp8_weight_version = mod.weight._version
+            done += 1
+    return done
+
+
+def use_fp8_weights(model, weights: str) -> bool:
+    """What a `weights=` argument means for `model`: False for "bf16"; for
+    "fp8", quantise the model's decode weights if they are not yet (or are
+    stale) and return True. The caller hands the answer down to the steps
+    it runs; nothing is kept on the model but the weights themselves."""
+    if weights not in ("bf16", "fp8"):
+        raise ValueError(f"weights must be 'bf16' or 'fp8', not {weights!r}")
+    if weights == "fp8":
+        quantize_decode_weights(model)
+    return weights == "fp8"
+
+
+def _fp8_weight(mod):
+    """The module's Fp8Weight, unless its weight was written since."""
+    w8 = getattr(mod, "fp8_weight", None)
+    if w8 is not None and mod.fp8_weight_version != mod.weight._version:
+        return None
+    return w8
+
+
+def _proj(mod, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
+    """x @ mod.weight^T through the decode GEMVs: with fp8 on, over the
+    module's fp8_weight where it has one and the kernel takes the rows,
+    else decode_linear over the (same-valued) bf16 weight."""
+    w8 = _fp8_weight(mod) if fp8 else None
+    if w8 is not None:
+        y = decode_linear_fp8(x, w8)
+        if y is not None:
+            return y
+    return decode_linear(x, mod.weight)
 
 
 class KVCache:
@@ -125,10 +196,10 @@ def _decode_attn(q, kk, vv, n_kv: int, ck=None, cv=None, pos_t=None):
 
 def _attn_cached(attn, x: torch.Tensor, cos: torch.Tensor,
                  sin: torch.Tensor, ck: torch.Tensor, cv: torch.Tensor,
-                 pos0: int) -> torch.Tensor:
+                 pos0: int, fp8: bool = False) -> torch.Tensor:
     cfg = attn.cfg
     B, S, _ = x.shape
-    qkv = decode_linear(x, attn.qkv_proj.weight)
+    qkv = _proj(attn.qkv_proj, x, fp8)
     q, k, v = qkv.split([attn.q_size, attn.kv_size, attn.kv_size], dim=-1)
     q = q.reshape(B, S, cfg.num_heads, cfg.head_dim)
     k = k.reshape(B, S, cfg.num_kv_heads, cfg.head_dim)
@@ -164,23 +235,25 @@ def _attn_cached(attn, x: torch.Tensor, cos: torch.Tensor,
         o = _decode_attn(q, kk, vv, cfg.num_kv_heads, ck, cv,
                          getattr(attn, "_pos_dec", None))
     o = o.transpose(1, 2).reshape(B, S, cfg.num_heads * cfg.head_dim)
-    return decode_linear(o, attn.o_proj.weight)
+    return _proj(attn.o_proj, o, fp8)
 
 
 
-def _mlp_cached(mlp, x: torch.Tensor) -> torch.Tensor:
+def _mlp_cached(mlp, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """SwiGLU MLP through the decode GEMV path: fused GEMV+SwiGLU when
     supported, else decode_linear + swiglu (both fall back to the
     library GEMM above 8 rows, so prefill takes the normal path)."""
-    from ..ops import decode_swiglu
-    h = decode_swiglu(x, mlp.gate_up_proj.weight)
+    gu8 = _fp8_weight(mlp.gate_up_proj) if fp8 else None
+    h = decode_swiglu_fp8(x, gu8) if gu8 is not None else None
+    if h is None:
+        h = decode_swiglu(x, mlp.gate_up_proj.weight)
     if h is None:
         gu = decode_linear(x, mlp.gate_up_proj.weight)
         h = swiglu_packed(gu.contiguous())
-    return decode_linear(h, mlp.down_proj.weight)
+    return _proj(mlp.down_proj, h, fp8)
 
 
-def _layers_cached(model, x: torch.Tensor, attend):
+def _layers_cached(model, x: torch.Tensor, attend, fp8: bool = False):
     """The blocks of a cached step whose attention works on the packed qkv
     projection (decode_graph._step_static, paged._step_paged,
     paged._prefill_paged): per block input norm -> qkv GEMV ->
@@ -193,10 +266,10 @@ def _layers_cached(model, x: torch.Tensor, attend):
     for li, blk in enumerate(model.blocks):
         normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
                                          residual, cfg.norm_eps)
-        qkv = decode_linear(normed, blk.attn.qkv_proj.weight)
+        qkv = _proj(blk.attn.qkv_proj, normed, fp8)
         o = attend(li, blk, qkv)
         o = o.reshape(B, S, cfg.num_heads * cfg.head_dim).to(x.dtype)
-        attn_out = decode_linear(o, blk.attn.o_proj.weight)
+        attn_out = _proj(blk.attn.o_proj, o, fp8)
         normed, residual = fused_rmsnorm(attn_out,
                                          blk.post_attn_norm_weight,
                                          residual, cfg.norm_eps)
@@ -204,14 +277,14 @@ def _layers_cached(model, x: torch.Tensor, attend):
         # path keeps routing on device (parallel/ep.py _decode_forward:
         # topk -> pointer-table GEMVs, fixed shapes, no host syncs), so MoE
         # blocks are stream-capturable too
-        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
+        x = _mlp_cached(blk.mlp, normed, fp8) if hasattr(blk, "mlp") \
             else blk.moe(normed)
     return x, residual
 
 
 @torch.no_grad()
 def _forward_cached(model: LlamaModel, tokens: torch.Tensor,
-                    cache: KVCache) -> torch.Tensor:
+                    cache: KVCache, fp8: bool = False) -> torch.Tensor:
     """Run tokens through the model appending to the cache; returns
     logits [B, S, V]."""
     cfg = model.cfg
@@ -237,18 +310,18 @@ def _forward_cached(model: LlamaModel, tokens: torch.Tensor,
         normed, residual = fused_rmsnorm(x, blk.input_norm_weight,
                                          residual, cfg.norm_eps)
         attn_out = _attn_cached(blk.attn, normed, cos, sin,
-                                cache.k[li], cache.v[li], pos0)
+                                cache.k[li], cache.v[li], pos0, fp8)
         normed, residual = fused_rmsnorm(attn_out,
                                          blk.post_attn_norm_weight,
                                          residual, cfg.norm_eps)
         # dense blocks carry .mlp; MoE blocks carry .moe (routing works
         # per token, so single-token decode steps route normally)
-        x = _mlp_cached(blk.mlp, normed) if hasattr(blk, "mlp") \
+        x = _mlp_cached(blk.mlp, normed, fp8) if hasattr(blk, "mlp") \
             else blk.moe(normed)
     cache.len = pos0 + tokens.shape[1]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
-    return decode_linear(normed, model.lm_head.weight)
+    return _proj(model.lm_head, normed, fp8)
 
 
 def _sample(logits: torch.Tensor, temperature: float, top_k: int,
@@ -268,20 +341,23 @@ def _sample(logits: torch.Tensor, temperature: float, top_k: int,
 def generate(model: LlamaModel, tokens: torch.Tensor,
              max_new_tokens: int, temperature: float = 0.0,
              top_k: int = 0, eos_token: Optional[int] = None,
-             seed: Optional[int] = None) -> torch.Tensor:
+             seed: Optional[int] = None,
+             weights: str = "bf16") -> torch.Tensor:
     """Autoregressive generation: prefill the prompt once, then KV-cached
-    one-token decode steps. temperature 0 = greedy. Returns
-    [B, prompt + generated]."""
+    one-token decode steps. temperature 0 = greedy. weights="fp8" streams
+    the decode projections from e4m3 weights (use_fp8_weights; the model
+    is quantised in place the first time). Returns [B, prompt + generated]."""
     was_training = model.training
     model.eval()
     try:
+        fp8 = use_fp8_weights(model, weights)
         B, S0 = tokens.shape
         cache = KVCache(model.cfg, B, S0 + max_new_tokens,
                         tokens.device, model.embed.weight.dtype)
         gen = None
         if seed is not None:
             gen = torch.Generator(device="cpu").manual_seed(seed)
-        last = _forward_cached(model, tokens, cache)[:, -1]
+        last = _forward_cached(model, tokens, cache, fp8)[:, -1]
         # opt-in hipGraph decode (see decode_graph.py for why not default)
         dec = None
         def _moe_graphable(moe):
@@ -299,7 +375,7 @@ def generate(model: LlamaModel, tokens: torch.Tensor,
         if (os.environ.get("AITJ_DECODE_GRAPH") == "1" and tokens.is_cuda
                 and max_new_tokens > 2 and graph_ok):
             from .decode_graph import GraphedDecoder
-            dec = GraphedDecoder(model, cache, B)
+            dec = GraphedDecoder(model, cache, B, fp8)
             dec.prime()
         out = tokens
         done = torch.zeros(B, dtype=torch.bool, device=tokens.device)
@@ -317,7 +393,7 @@ def generate(model: LlamaModel, tokens: torch.Tensor,
             if eos_token is not None and bool(done.all()):
                 break
             last = dec.step(nxt) if dec is not None else \
-                _forward_cached(model, nxt[:, None], cache)[:, -1]
+                _forward_cached(model, nxt[:, None], cache, fp8)[:, -1]
         return out
     finally:
         if was_training:
@@ -347,7 +423,8 @@ def _ngram_proposal(ctx: list, k: int) -> list:
 @torch.no_grad()
 def generate_lookup(model, tokens: torch.Tensor, max_new_tokens: int,
                     lookup_k: int = 8,
-                    eos_token: Optional[int] = None) -> torch.Tensor:
+                    eos_token: Optional[int] = None,
+                    weights: str = "bf16") -> torch.Tensor:
     """Greedy generation with prompt-lookup speculative decoding
     (batch 1): propose up to lookup_k continuation tokens from an
     earlier occurrence of the current n-gram, verify them in ONE
@@ -361,10 +438,11 @@ def generate_lookup(model, tokens: torch.Tensor, max_new_tokens: int,
     was_training = model.training
     model.eval()
     try:
+        fp8 = use_fp8_weights(model, weights)
         B, S0 = tokens.shape
         cache = KVCache(model.cfg, B, S0 + max_new_tokens + lookup_k + 1,
                         tokens.device, model.embed.weight.dtype)
-        logits = _forward_cached(model, tokens, cache)
+        logits = _forward_cached(model, tokens, cache, fp8)
         cur = int(logits[0, -1].argmax())
         ctx = tokens[0].tolist() + [cur]
         produced = 1
@@ -373,7 +451,7 @@ def generate_lookup(model, tokens: torch.Tensor, max_new_tokens: int,
             prop = _ngram_proposal(ctx, min(lookup_k, room)) if room > 1                 else []
             step = torch.tensor([[cur] + prop], device=tokens.device)
             pos0 = cache.len
-            logits = _forward_cached(model, step, cache)
+            logits = _forward_cached(model, step, cache, fp8)
             nxt = logits[0].argmax(dim=-1).tolist()   # true tokens
             accepted = 0
             for j, pj in enumerate(prop):

@@ -45,12 +45,12 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..ops import (decode_attention_paged, decode_linear, fused_rmsnorm,
+from ..ops import (decode_attention_paged, fused_rmsnorm,
                    prefill_attention_paged, prefill_work, reference,
                    rope_cache_paged, rope_cache_paged_rows,
                    verify_attention_paged)
 from .generate import (KVCache, _forward_cached, _layers_cached,
-                       _ngram_proposal, _sample)
+                       _ngram_proposal, _proj, _sample, use_fp8_weights)
 
 PAGE_ROWS = reference.PAGE_ROWS
 
@@ -233,8 +233,8 @@ class PagedKVCache:
 
 
 @torch.no_grad()
-def _step_paged(model, cur: torch.Tensor,
-                cache: PagedKVCache) -> torch.Tensor:
+def _step_paged(model, cur: torch.Tensor, cache: PagedKVCache,
+                fp8: bool = False) -> torch.Tensor:
     """One decode step for every slot of a paged cache: cur [B, 1] token
     ids (B = cache.max_slots; idle slots carry any valid id) -> logits
     [B, V]. decode_graph._step_static with the two paged calls; positions
@@ -258,17 +258,18 @@ def _step_paged(model, cur: torch.Tensor,
                 scale)
         return o
 
-    x, residual = _layers_cached(model, model.embed(cur), attend)  # [B, 1, H]
+    x, residual = _layers_cached(model, model.embed(cur), attend,
+                                 fp8)                          # [B, 1, H]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
-    logits = decode_linear(normed, model.lm_head.weight)
+    logits = _proj(model.lm_head, normed, fp8)
     cache.pos.add_((cache.pos >= 0).to(cache.pos.dtype))   # in-graph advance
     return logits.reshape(B, -1)
 
 
 @torch.no_grad()
 def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
-                   chunks, last_rows) -> torch.Tensor:
+                   chunks, last_rows, fp8: bool = False) -> torch.Tensor:
     """One packed prefill forward straight into the pages: tokens [1, T]
     are the concatenated chunks = [(slot, pos0, n_tokens), ...] of several
     sequences, whose pages up to each chunk's last row the caller owns
@@ -300,7 +301,7 @@ def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
         return o
 
     x, residual = _layers_cached(model, model.embed(tokens),   # [1, T, H]
-                                 attend)
+                                 attend, fp8)
     if not last_rows:                 # no prompt ends in this batch
         return x.new_zeros(0, model.lm_head.weight.shape[0])
     rows = torch.tensor(list(last_rows), dtype=torch.long, device=dev)
@@ -310,13 +311,13 @@ def _prefill_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
     normed, _ = fused_rmsnorm(x.contiguous(), model.final_norm_weight,
                               None if residual is None
                               else residual.contiguous(), cfg.norm_eps)
-    logits = decode_linear(normed, model.lm_head.weight)
+    logits = _proj(model.lm_head, normed, fp8)
     return logits.reshape(len(rows), -1)
 
 
 @torch.no_grad()
 def _verify_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
-                  n_q: torch.Tensor) -> torch.Tensor:
+                  n_q: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """One speculative verify forward for every slot of a paged cache:
     tokens [B, T] (B = cache.max_slots, T <= 8); token t of slot b sits at
     position cache.pos[b] + t, and only the first n_q[b] (int32 [B], device)
@@ -357,10 +358,10 @@ def _verify_paged(model, tokens: torch.Tensor, cache: PagedKVCache,
                 n_q, scale)
         return o
 
-    x, residual = _layers_cached(model, model.embed(tokens), attend)
+    x, residual = _layers_cached(model, model.embed(tokens), attend, fp8)
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
-    logits = decode_linear(normed, model.lm_head.weight)
+    logits = _proj(model.lm_head, normed, fp8)
     return logits.reshape(B, T, -1)
 
 
@@ -431,13 +432,19 @@ class PagedEngine:
     one _verify_paged forward, and each keeps the matching prefix plus the
     bonus token. The tokens are those of lookup_k = 0; only the number of
     steps changes. Eager only: with graph=True it is a ValueError.
+
+    weights="fp8" streams the decode projections of every step of up to 16
+    rows from e4m3 weights (generate.use_fp8_weights; the model is
+    quantised in place the first time, and computes the same logits either
+    way up to summation order).
     """
 
     def __init__(self, model, max_slots: int = 8,
                  n_pages: Optional[int] = None,
                  max_pages_per_seq: Optional[int] = None,
                  graph: bool = False, prefill: str = "contiguous",
-                 prefill_chunk: int = 512, lookup_k: int = 0):
+                 prefill_chunk: int = 512, lookup_k: int = 0,
+                 weights: str = "bf16"):
         if not 0 <= lookup_k <= 7:
             raise ValueError("lookup_k must be in 0..7")
         if lookup_k > 0 and graph:
@@ -455,6 +462,7 @@ class PagedEngine:
         self.prefill_chunk = int(prefill_chunk)
         self.prefill_steps = 0
         self._admit_seq = 0
+        self.fp8 = use_fp8_weights(model, weights)   # after the checks
         self.model = model
         self.device = model.embed.weight.device
         if n_pages is None:
@@ -574,7 +582,7 @@ class PagedEngine:
                                   device=self.device)
             tmp = KVCache(self.model.cfg, 1, req.prompt_len, self.device,
                           self.model.embed.weight.dtype)
-            last = _forward_cached(self.model, prompt, tmp)[0, -1]
+            last = _forward_cached(self.model, prompt, tmp, self.fp8)[0, -1]
             self.cache.load_prefix(slot, [k[0] for k in tmp.k],
                                    [v[0] for v in tmp.v], req.prompt_len)
             tok = self._pick(req, last, None)
@@ -632,7 +640,7 @@ class PagedEngine:
             return
         tokens = torch.tensor([toks], dtype=torch.long, device=self.device)
         logits = _prefill_paged(self.model, tokens, self.cache, chunks,
-                                last_rows)
+                                last_rows, self.fp8)
         self.prefill_steps += 1
         for slot, p0, n in chunks:
             self.slots[slot].n_prefilled = p0 + n
@@ -654,7 +662,8 @@ class PagedEngine:
     def _decode(self) -> torch.Tensor:
         self.cur.copy_(torch.tensor(self._host_cur, dtype=torch.long))
         if not self.graph_mode:
-            return _step_paged(self.model, self.cur[:, None], self.cache)
+            return _step_paged(self.model, self.cur[:, None], self.cache,
+                               self.fp8)
         if self._graph is None:
             self._capture()
         self._graph.replay()
@@ -670,12 +679,13 @@ class PagedEngine:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
-                _step_paged(self.model, self.cur[:, None], self.cache)
+                _step_paged(self.model, self.cur[:, None], self.cache,
+                            self.fp8)
         torch.cuda.current_stream().wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._graph_logits = _step_paged(self.model, self.cur[:, None],
-                                             self.cache)
+                                             self.cache, self.fp8)
         self._graph = g
         self.cache.pos.copy_(saved)
 
@@ -702,7 +712,8 @@ class PagedEngine:
             cache.ensure_row(req.slot, cache.host_pos[req.slot] + len(row) - 1)
         logits = _verify_paged(
             self.model, torch.tensor(toks, dtype=torch.long).to(self.device),
-            cache, torch.tensor(n_q, dtype=torch.int32).to(self.device))
+            cache, torch.tensor(n_q, dtype=torch.int32).to(self.device),
+            self.fp8)
         self.steps += 1
         greedy = None
         if any(r.temperature <= 0.0 for r in active):
@@ -807,7 +818,8 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
                     n_pages: Optional[int] = None,
                     graph: bool = False,
                     prefill_chunk: Optional[int] = None,
-                    lookup_k: int = 0) -> List[torch.Tensor]:
+                    lookup_k: int = 0,
+                    weights: str = "bf16") -> List[torch.Tensor]:
     """generate() for prompts of DIFFERENT lengths: every prompt is its
     own engine request (own position, own pages, own generator seeded
     with `seed`), decoded together `max_slots` at a time. Returns one
@@ -828,7 +840,7 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
             if prefill_chunk else {}
         eng = PagedEngine(model, max_slots=max_slots, n_pages=n_pages,
                           max_pages_per_seq=need, graph=graph,
-                          lookup_k=lookup_k, **paged)
+                          lookup_k=lookup_k, weights=weights, **paged)
         ids = [eng.submit(p, max_new_tokens, temperature, top_k, eos_token,
                           seed) for p in prompts]
         done = eng.run()

@@ -10,7 +10,9 @@ from .functional import (
     decode_attention,
     decode_attention_paged,
     decode_linear,
+    decode_linear_fp8,
     decode_swiglu,
+    decode_swiglu_fp8,
     fused_cross_entropy,
     fused_rmsnorm,
     dispatch_rows,
@@ -32,7 +34,9 @@ __all__ = [
     "decode_attention",
     "decode_attention_paged",
     "decode_linear",
+    "decode_linear_fp8",
     "decode_swiglu",
+    "decode_swiglu_fp8",
     "dispatch_rows",
     "gather_rows",
     "moe_combine",

@@ -550,6 +550,55 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.linear(x, weight)
 
 
+def _fp8_rows(x: torch.Tensor, w8) -> int:
+    """Rows of x if the fp8 decode GEMVs take (x, w8), else 0."""
+    K = x.shape[-1]
+    rows = x.numel() // K if K else 0
+    if K != w8.K or not 1 <= rows <= 16:
+        return 0
+    if x.is_cuda and x.dtype != torch.bfloat16:
+        return 0
+    return rows
+
+
+def decode_linear_fp8(x: torch.Tensor, w8) -> Optional[torch.Tensor]:
+    """y = x @ dequant(w8)^T for 1..16 rows of bf16 x over an e4m3 weight
+    (ops/fp8_weight.py): the matrix-core weight-only GEMV (hip/ops.hip
+    gemv_fp8), half the weight bytes of decode_linear. Returns None when it
+    does not take the call (rows, K, dtype, a gate|up weight); off the GPU
+    the reference twin runs. Inference-only."""
+    rows = _fp8_rows(x, w8)
+    if not rows or w8.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_linear_fp8(x, w8)
+    x2 = x.reshape(rows, w8.K).contiguous()
+    y = torch.empty(rows, w8.M, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemv_fp8(native.stream_ptr(), _ptr(w8.packed),
+                         _ptr(w8.scale), _ptr(x2), _ptr(y), w8.M, w8.K, rows)
+    native.check_rc(rc, "gemv_fp8", f"M={w8.M} K={w8.K} N={rows}")
+    return y.reshape(*x.shape[:-1], w8.M)
+
+
+def decode_swiglu_fp8(x: torch.Tensor, gu8) -> Optional[torch.Tensor]:
+    """silu(x @ Wg^T) * (x @ Wu^T) over a packed e4m3 gate|up weight in one
+    kernel (hip/ops.hip gemv_fp8_swiglu): [..., F] for 1..16 rows, None
+    otherwise, like decode_linear_fp8."""
+    rows = _fp8_rows(x, gu8)
+    if not rows or not gu8.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_swiglu_fp8(x, gu8)
+    F = gu8.M // 2
+    x2 = x.reshape(rows, gu8.K).contiguous()
+    y = torch.empty(rows, F, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemv_fp8_swiglu(native.stream_ptr(), _ptr(gu8.packed),
+                                _ptr(gu8.scale), _ptr(x2), _ptr(y), F,
+                                gu8.K, rows)
+    native.check_rc(rc, "gemv_fp8_swiglu", f"F={F} K={gu8.K} N={rows}")
+    return y.reshape(*x.shape[:-1], F)
+
+
 # ---------------------------------------------------------------------------
 # Fused cross-entropy
 # ---------------------------------------------------------------------------

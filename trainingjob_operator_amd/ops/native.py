@@ -72,6 +72,11 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
          i)
     _sig(lib.gemv_bf16, [vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_swiglu, [vp, vp, vp, vp, i, i, i], i)
+    # fp8 decode GEMVs: (packed e4m3 weight, fp32 row scales, x, y, M | F,
+    # K, N <= 16); gemv_fp8_split(tiles, K) is their split-K rule (host)
+    _sig(lib.gemv_fp8, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemv_fp8_swiglu, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemv_fp8_split, [i, i], i)
     _sig(lib.gemv_moe_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i], i)
     _sig(lib.gemv_moe, [vp, vp, vp, vp, vp, i, i, i, i], i)
     _sig(lib.attn_decode, [vp, vp, vp, vp, vp, vp, vp,

@@ -430,3 +430,17 @@ def attn_merge_(o_acc: torch.Tensor, lse_acc: torch.Tensor,
     wb = torch.exp(lse_blk.float() - lse_new).masked_fill(dead, 0.0)
     o_acc.mul_(wa).add_(o_blk.float() * wb.unsqueeze(-1))
     lse_acc.copy_(lse_new)
+
+
+def decode_linear_fp8(x: torch.Tensor, w8) -> torch.Tensor:
+    """Twin of hip/ops.hip gemv_fp8: dequantise the e4m3 weight, multiply in
+    fp32, round once to x's dtype (bf16 for the bf16 x the kernel takes)."""
+    y = x.float() @ w8.dequant().to(x.device).t()
+    return y.to(x.dtype)
+
+
+def decode_swiglu_fp8(x: torch.Tensor, gu8) -> torch.Tensor:
+    """Twin of gemv_fp8_swiglu over the packed gate|up weight [2F, K]."""
+    gu = x.float() @ gu8.dequant().to(x.device).t()
+    g, u = gu.chunk(2, dim=-1)
+    return (torch.nn.functional.silu(g) * u).to(x.dtype)
