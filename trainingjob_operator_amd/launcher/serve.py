@@ -7,7 +7,7 @@ families an OpenAI-ish token-in/token-out endpoint on an MI355X node:
     python -m trainingjob_operator_amd.launcher.serve \
         --model llama3-8b --port 8000 [--ckpt-dir DIR] [--graph]
         [--paged [--max-slots N] [--pool-pages N] [--prefill-chunk N]
-         [--lookup-k N]]
+         [--lookup-k N] [--kv fp8]]
 
 The API is deliberately token-level (``prompt_tokens`` → ``tokens``):
 tokenizers are workload assets the cluster may not have offline, and the
@@ -26,7 +26,9 @@ the pages, at most N prompt tokens per step; 0 (default) prefills every
 request at once on a temporary contiguous cache. --lookup-k N (1..7)
 makes every decode step a speculative verify step: greedy requests draft
 up to N tokens by prompt lookup and all slots verify them in one forward
-(same tokens, fewer steps; not together with --graph).
+(same tokens, fewer steps; not together with --graph). --kv fp8 keeps the
+pages in e4m3 with per-row scales (half the bytes per cached token; decode
+on the fp8 KV kernels; not together with --prefill-chunk or --lookup-k).
 
 Endpoints:
     GET  /healthz   liveness + model name
@@ -55,14 +57,15 @@ _PAGED_GAUGES = {}
 def create_app(model, model_name: str = "model", paged: bool = False,
                max_slots: int = 8, pool_pages: Optional[int] = None,
                prefill_chunk: int = 0, lookup_k: int = 0,
-               weights: str = "bf16"):
+               weights: str = "bf16", kv: str = "bf16"):
     """Build the FastAPI app around an already-constructed model (tests
     pass a CPU llama-tiny; the CLI builds the named config on cuda:0).
     paged=True serves /generate through a PagedEngine of `max_slots`
     sequences over `pool_pages` 64-row KV pages (default 32 per slot);
     prefill_chunk > 0 selects the engine's paged prefill with that many
     prompt tokens per step, lookup_k > 0 its prompt-lookup speculation.
-    weights="fp8" decodes from e4m3 weights on every route."""
+    weights="fp8" decodes from e4m3 weights on every route; kv="fp8"
+    (paged only) keeps the KV pages in e4m3."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
@@ -113,6 +116,9 @@ def create_app(model, model_name: str = "model", paged: bool = False,
 
     engine = None
     stop = threading.Event()
+    if kv != "bf16" and not paged:
+        raise ValueError("kv='fp8' is a property of the paged cache: it "
+                         "needs paged=True")
     if paged:
         import os
 
@@ -121,7 +127,7 @@ def create_app(model, model_name: str = "model", paged: bool = False,
         engine = PagedEngine(
             model, max_slots=max_slots, n_pages=pool_pages,
             graph=os.environ.get("AITJ_DECODE_GRAPH") == "1",
-            lookup_k=lookup_k, weights=weights,
+            lookup_k=lookup_k, weights=weights, kv=kv,
             **({"prefill": "paged", "prefill_chunk": int(prefill_chunk)}
                if prefill_chunk else {}))
         if mx:
@@ -201,7 +207,7 @@ def create_app(model, model_name: str = "model", paged: bool = False,
                         pages_free=engine.cache.pages_free,
                         prefill_chunk=(engine.prefill_chunk
                                        if engine.prefill == "paged" else 0),
-                        lookup_k=engine.lookup_k)
+                        lookup_k=engine.lookup_k, kv=engine.kv)
         return body
 
     @app.get("/metrics")
@@ -344,6 +350,10 @@ def main(argv=None):
                     help="fp8: quantise the decode projections to e4m3 "
                          "(per-row power-of-two scales) and stream those in "
                          "every step of up to 16 rows")
+    ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16",
+                    help="with --paged: fp8 keeps the KV pages in e4m3 with "
+                         "one scale per row and kv head (132 bytes per row "
+                         "and head instead of 256)")
     args = ap.parse_args(argv)
     if args.graph:
         os.environ["AITJ_DECODE_GRAPH"] = "1"
@@ -356,7 +366,8 @@ def main(argv=None):
     app = create_app(model, args.model, paged=args.paged,
                      max_slots=args.max_slots, pool_pages=args.pool_pages,
                      prefill_chunk=args.prefill_chunk,
-                     lookup_k=args.lookup_k, weights=args.weights)
+                     lookup_k=args.lookup_k, weights=args.weights,
+                     kv=args.kv)
     uvicorn.run(app, host=args.host, port=args.port, log_level="info")
 
 

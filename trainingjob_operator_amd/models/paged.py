@@ -30,6 +30,12 @@ device (ops.rope_cache_paged, ops.decode_attention_paged):
     back by setting each slot's position;
   * generate_ragged — prompts of different lengths in, one tensor each out.
 
+kv_dtype="fp8" (PagedEngine(kv="fp8")) keeps the pages in e4m3 with one
+power-of-two scale per (row, kv head): 132 bytes per row and head where bf16
+takes 256 (format: ops/reference.py "fp8 KV cache"). The decode step then
+writes through ops.rope_cache_paged_fp8 and attends through
+ops.decode_attention_paged_fp8; head_dim must be 128.
+
 Admission reserves ceil((prompt + max_new_tokens) / 64) pages up front
 and takes the physical pages as the position crosses page boundaries, so
 an admitted request can always finish; one that does not fit waits in the
@@ -45,10 +51,10 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ..ops import (decode_attention_paged, fused_rmsnorm,
-                   prefill_attention_paged, prefill_work, reference,
-                   rope_cache_paged, rope_cache_paged_rows,
-                   verify_attention_paged)
+from ..ops import (decode_attention_paged, decode_attention_paged_fp8,
+                   fused_rmsnorm, prefill_attention_paged, prefill_work,
+                   reference, rope_cache_paged, rope_cache_paged_fp8,
+                   rope_cache_paged_rows, verify_attention_paged)
 from .generate import (KVCache, _forward_cached, _layers_cached,
                        _ngram_proposal, _proj, _sample, use_fp8_weights)
 
@@ -69,12 +75,31 @@ class PagedKVCache:
     = idle slot). Both are updated in place, so a captured step keeps
     reading the same buffers. The host keeps the free list, the pages
     each slot owns and reserved, and a mirror of `pos`.
+
+    kv_dtype="fp8": `k` and `v` are uint8 pools of the same shape (e4m3
+    bytes; `v` as fragment images) and `kv_scale` holds the per-layer fp32
+    [n_pages, n_kv, 2, 64] scales (ops/reference.py "fp8 KV cache");
+    `dtype` is then only what load_prefix's callers compute in.
     """
 
     def __init__(self, cfg, n_pages: int, max_slots: int,
-                 max_pages_per_seq: int, device, dtype):
+                 max_pages_per_seq: int, device, dtype,
+                 kv_dtype: str = "bf16"):
         assert n_pages > 0 and max_slots > 0 and max_pages_per_seq > 0
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', not "
+                             f"{kv_dtype!r}")
+        if kv_dtype == "fp8" and cfg.head_dim != 128:
+            raise ValueError("the fp8 KV cache is defined for head_dim 128, "
+                             f"not {cfg.head_dim}")
+        self.kv_dtype = kv_dtype
         shape = (n_pages, cfg.num_kv_heads, PAGE_ROWS, cfg.head_dim)
+        if kv_dtype == "fp8":
+            dtype = torch.uint8
+            self.kv_scale: List[torch.Tensor] = [
+                torch.ones(n_pages, cfg.num_kv_heads, 2, PAGE_ROWS,
+                           device=device, dtype=torch.float32)
+                for _ in range(cfg.num_layers)]
         self.k: List[torch.Tensor] = [
             torch.zeros(shape, device=device, dtype=dtype)
             for _ in range(cfg.num_layers)]
@@ -172,13 +197,25 @@ class PagedKVCache:
         """Scatter rows 0..length-1 of a contiguous cache (per layer
         [n_kv, >=length, D]) into the slot's pages and put the slot at
         position `length`, the row its next token will occupy. Torch ops,
-        off the hot path."""
+        off the hot path. An fp8 cache quantises the rows through the twin
+        (reference.kv_fp8_quant_pages)."""
         assert 0 < length
         self.ensure_row(slot, length)
         n_full = pages_for(length)
         pages = torch.tensor(self.owned[slot][:n_full], dtype=torch.long,
                              device=self.pos.device)
         pad = n_full * PAGE_ROWS - length
+        if self.kv_dtype == "fp8":
+            for li, (k, v) in enumerate(zip(k_layers, v_layers)):
+                n_kv, _, D = k.shape
+                k, v = (torch.nn.functional.pad(t[:, :length],
+                                                (0, 0, 0, pad))
+                        .reshape(n_kv, n_full, PAGE_ROWS, D).transpose(0, 1)
+                        for t in (k, v))
+                (self.k[li][pages], self.v[li][pages],
+                 self.kv_scale[li][pages]) = reference.kv_fp8_quant_pages(k, v)
+            self.set_pos(slot, length)
+            return
         for pool, layers in ((self.k, k_layers), (self.v, v_layers)):
             for li, src in enumerate(layers):
                 src = src[:, :length].to(pool[li].dtype)
@@ -245,6 +282,19 @@ def _step_paged(model, cur: torch.Tensor, cache: PagedKVCache,
     B = cur.shape[0]
     scale = 1.0 / math.sqrt(cfg.head_dim)
 
+    def attend_fp8(li, blk, qkv):
+        pools = (cache.k[li], cache.v[li], cache.kv_scale[li])
+        q = rope_cache_paged_fp8(qkv.reshape(B, -1), *pools, model.inv_freq,
+                                 cache.block_table, cache.pos,
+                                 cfg.num_heads, cfg.num_kv_heads)
+        q = q[:, :, None, :]                               # [B, nh, 1, D]
+        o = decode_attention_paged_fp8(q, *pools, cache.block_table,
+                                       cache.pos, scale)
+        if o is None:                 # off-GPU or more than 16 q per kv head
+            o = reference.decode_attention_paged_fp8(
+                q, *pools, cache.block_table, cache.pos, scale)
+        return o
+
     def attend(li, blk, qkv):
         q = rope_cache_paged(qkv.reshape(B, -1), cache.k[li], cache.v[li],
                              model.inv_freq, cache.block_table, cache.pos,
@@ -258,8 +308,9 @@ def _step_paged(model, cur: torch.Tensor, cache: PagedKVCache,
                 scale)
         return o
 
-    x, residual = _layers_cached(model, model.embed(cur), attend,
-                                 fp8)                          # [B, 1, H]
+    x, residual = _layers_cached(
+        model, model.embed(cur),
+        attend_fp8 if cache.kv_dtype == "fp8" else attend, fp8)  # [B, 1, H]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)
     logits = _proj(model.lm_head, normed, fp8)
@@ -437,6 +488,14 @@ class PagedEngine:
     rows from e4m3 weights (generate.use_fp8_weights; the model is
     quantised in place the first time, and computes the same logits either
     way up to summation order).
+
+    kv="fp8" keeps the pages in e4m3 (PagedKVCache(kv_dtype="fp8")): half
+    the bytes per cached row, so twice the rows in the same pool bytes (the
+    default n_pages is unchanged; pass twice as many to use them), and the
+    decode step runs on the fp8 write and MFMA decode kernels. Composes with
+    weights="fp8" and graph=True; head_dim 128 only. The paged prefill and
+    the speculative verify kernels do not read fp8 pages yet: prefill="paged"
+    or lookup_k > 0 with kv="fp8" is a ValueError.
     """
 
     def __init__(self, model, max_slots: int = 8,
@@ -444,9 +503,24 @@ class PagedEngine:
                  max_pages_per_seq: Optional[int] = None,
                  graph: bool = False, prefill: str = "contiguous",
                  prefill_chunk: int = 512, lookup_k: int = 0,
-                 weights: str = "bf16"):
+                 weights: str = "bf16", kv: str = "bf16"):
         if not 0 <= lookup_k <= 7:
             raise ValueError("lookup_k must be in 0..7")
+        if kv not in ("bf16", "fp8"):
+            raise ValueError(f"kv must be 'bf16' or 'fp8', not {kv!r}")
+        if kv == "fp8" and prefill == "paged":
+            raise ValueError("kv='fp8' needs prefill='contiguous': the paged "
+                             "prefill kernels (rope_cache_paged_rows, "
+                             "attn_prefill_paged) on fp8 pages are a "
+                             "follow-up")
+        if kv == "fp8" and lookup_k > 0:
+            raise ValueError("kv='fp8' needs lookup_k=0: the speculative "
+                             "verify kernel (attn_verify_paged) on fp8 pages "
+                             "is a follow-up")
+        if kv == "fp8" and model.cfg.head_dim != 128:
+            raise ValueError("kv='fp8' is defined for head_dim 128, not "
+                             f"{model.cfg.head_dim}")
+        self.kv = kv
         if lookup_k > 0 and graph:
             raise ValueError("lookup_k > 0 runs eagerly: graph capture of "
                              "the verify step is not wired in yet")
@@ -472,7 +546,7 @@ class PagedEngine:
         self.max_slots = max_slots
         self.cache = PagedKVCache(model.cfg, n_pages, max_slots,
                                   max_pages_per_seq, self.device,
-                                  model.embed.weight.dtype)
+                                  model.embed.weight.dtype, kv_dtype=kv)
         self.cur = torch.zeros(max_slots, dtype=torch.long,
                                device=self.device)
         self._host_cur = [0] * max_slots
@@ -819,7 +893,8 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
                     graph: bool = False,
                     prefill_chunk: Optional[int] = None,
                     lookup_k: int = 0,
-                    weights: str = "bf16") -> List[torch.Tensor]:
+                    weights: str = "bf16",
+                    kv: str = "bf16") -> List[torch.Tensor]:
     """generate() for prompts of DIFFERENT lengths: every prompt is its
     own engine request (own position, own pages, own generator seeded
     with `seed`), decoded together `max_slots` at a time. Returns one
@@ -827,7 +902,7 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
     None or 0 = prefill each prompt at once on a contiguous cache; N > 0 =
     paged prefill, at most N prompt tokens per engine step. lookup_k > 0:
     prompt-lookup speculation for the greedy requests (PagedEngine), same
-    tokens in fewer steps."""
+    tokens in fewer steps. kv="fp8": the pages in e4m3 (PagedEngine)."""
     was_training = model.training
     model.eval()
     try:
@@ -840,7 +915,8 @@ def generate_ragged(model, prompts: List[torch.Tensor], max_new_tokens: int,
             if prefill_chunk else {}
         eng = PagedEngine(model, max_slots=max_slots, n_pages=n_pages,
                           max_pages_per_seq=need, graph=graph,
-                          lookup_k=lookup_k, weights=weights, **paged)
+                          lookup_k=lookup_k, weights=weights, kv=kv,
+                          **paged)
         ids = [eng.submit(p, max_new_tokens, temperature, top_k, eos_token,
                           seed) for p in prompts]
         done = eng.run()

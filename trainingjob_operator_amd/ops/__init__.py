@@ -9,6 +9,7 @@ from .functional import (
     apply_rope,
     decode_attention,
     decode_attention_paged,
+    decode_attention_paged_fp8,
     decode_linear,
     decode_linear_fp8,
     decode_swiglu,
@@ -22,6 +23,7 @@ from .functional import (
     prefill_attention_paged,
     prefill_work,
     rope_cache_paged,
+    rope_cache_paged_fp8,
     rope_cache_paged_rows,
     swiglu,
     swiglu_packed,
@@ -33,6 +35,7 @@ __all__ = [
     "apply_rope",
     "decode_attention",
     "decode_attention_paged",
+    "decode_attention_paged_fp8",
     "decode_linear",
     "decode_linear_fp8",
     "decode_swiglu",
@@ -46,6 +49,7 @@ __all__ = [
     "prefill_attention_paged",
     "prefill_work",
     "rope_cache_paged",
+    "rope_cache_paged_fp8",
     "rope_cache_paged_rows",
     "swiglu",
     "verify_attention_paged",

@@ -349,6 +349,94 @@ def rope_cache_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
     return q
 
 
+def _fp8_pools_ok(k8: torch.Tensor, v8: torch.Tensor,
+                  sc: torch.Tensor) -> bool:
+    """The three pools of an fp8 KV cache as the kernels take them."""
+    return (k8.is_cuda and k8.dtype == torch.uint8 and k8.dim() == 4
+            and k8.shape[2:] == (reference.PAGE_ROWS, 128)
+            and v8.dtype == torch.uint8 and v8.shape == k8.shape
+            and sc.dtype == torch.float32
+            and sc.shape == (k8.shape[0], k8.shape[1], 2,
+                             reference.PAGE_ROWS)
+            and k8.is_contiguous() and v8.is_contiguous()
+            and sc.is_contiguous())
+
+
+def decode_attention_paged_fp8(q: torch.Tensor, k8_pool: torch.Tensor,
+                               v8_pool: torch.Tensor, sc_pool: torch.Tensor,
+                               block_table: torch.Tensor, pos: torch.Tensor,
+                               scale: float) -> Optional[torch.Tensor]:
+    """decode_attention_paged over an fp8 KV cache (hip/ops.hip
+    attn_decode_paged_fp8; format in reference.py): k8/v8 uint8 [n_pages,
+    n_kv, 64, 128] (v8 as fragment images), sc fp32 [n_pages, n_kv, 2, 64].
+    One MFMA wave per (kv head, page) serves the whole GQA group, so G =
+    H / n_kv <= 16. Same contract as decode_attention_paged: [B, H, 1, D],
+    or None when the shape is unsupported (the caller falls back to
+    reference.decode_attention_paged_fp8). Inference-only."""
+    B, H, S, D = q.shape
+    n_kv = k8_pool.shape[1] if k8_pool.dim() == 4 else 0
+    G = H // n_kv if n_kv and H % n_kv == 0 else 0
+    if not (q.is_cuda and q.dtype == torch.bfloat16 and D == 128
+            and S == 1 and 1 <= G <= 16
+            and _fp8_pools_ok(k8_pool, v8_pool, sc_pool)
+            and block_table.dtype == torch.int32
+            and block_table.dim() == 2 and block_table.shape[0] == B
+            and block_table.is_contiguous()
+            and pos.dtype == torch.int64 and pos.shape == (B,)
+            and pos.is_contiguous()):
+        return None
+    lib = _hip()
+    max_pages = block_table.shape[1]
+    q2 = q.reshape(B, H, D).contiguous()
+    partial = torch.empty(B, n_kv, max_pages, G, 130, dtype=torch.float32,
+                          device=q.device)
+    o = torch.empty(B, H, D, dtype=torch.bfloat16, device=q.device)
+    rc = lib.attn_decode_paged_fp8(
+        native.stream_ptr(), _ptr(q2), _ptr(k8_pool), _ptr(v8_pool),
+        _ptr(sc_pool), _ptr(block_table), _ptr(pos), _ptr(partial), _ptr(o),
+        B, H, n_kv, k8_pool.shape[0], max_pages, scale)
+    native.check_rc(rc, "attn_decode_paged_fp8",
+                    f"H={H} n_kv={n_kv} max_pages={max_pages}")
+    return o[:, :, None, :]
+
+
+def rope_cache_paged_fp8(qkv: torch.Tensor, k8_pool: torch.Tensor,
+                         v8_pool: torch.Tensor, sc_pool: torch.Tensor,
+                         inv_freq: torch.Tensor, block_table: torch.Tensor,
+                         pos: torch.Tensor, num_heads: int,
+                         num_kv_heads: int) -> torch.Tensor:
+    """rope_cache_paged into an fp8 KV cache (hip/ops.hip
+    rope_cache_paged_fp8): ropes q into the returned [B, nh, 128] buffer;
+    ropes k, quantises k and v per (row, kv head) and stores the K row, the
+    V image bytes and the two scales at row pos[b] % 64 of page
+    block_table[b][pos[b] // 64], in place. An idle slot writes nothing and
+    gets a zero q. Off-GPU (or fp32) the torch reference does the same."""
+    B = qkv.shape[0]
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16
+            and inv_freq.dtype == torch.float32
+            and _fp8_pools_ok(k8_pool, v8_pool, sc_pool)):
+        return reference.rope_cache_paged_fp8(
+            qkv, k8_pool, v8_pool, sc_pool, inv_freq, block_table, pos,
+            num_heads, num_kv_heads)
+    assert block_table.dtype == torch.int32 and block_table.is_contiguous()
+    assert block_table.shape[0] == B and pos.shape == (B,)
+    assert pos.dtype == torch.int64 and pos.is_contiguous()
+    assert k8_pool.shape[1] == num_kv_heads
+    assert qkv.numel() == B * (num_heads + 2 * num_kv_heads) * 128
+    assert inv_freq.numel() == 64 and inv_freq.is_contiguous()
+    lib = _hip()
+    qkv = qkv.contiguous()
+    q = torch.empty(B, num_heads, 128, dtype=torch.bfloat16,
+                    device=qkv.device)
+    rc = lib.rope_cache_paged_fp8(
+        native.stream_ptr(), _ptr(qkv), _ptr(q), _ptr(k8_pool),
+        _ptr(v8_pool), _ptr(sc_pool), _ptr(inv_freq), _ptr(block_table),
+        _ptr(pos), B, num_heads, num_kv_heads, k8_pool.shape[0],
+        block_table.shape[1])
+    native.check_rc(rc, "rope_cache_paged_fp8", f"B={B}")
+    return q
+
+
 def rope_cache_paged_rows(qkv: torch.Tensor, k_pool: torch.Tensor,
                           v_pool: torch.Tensor, inv_freq: torch.Tensor,
                           block_table: torch.Tensor, tok_slot: torch.Tensor,

@@ -1609,6 +1609,281 @@ void gemv_fp8_kernel(const gf8_u32x4* __restrict__ w8,
 
 
 // ---------------------------------------------------------------------------
+// fp8 KV cache (format: ops/reference.py "fp8 KV cache", the torch twin these
+// two kernels reproduce byte for byte). Per layer a K byte pool [n_pages,
+// n_kv, 64, 128] row-major, a V byte pool of the same size holding one
+// 8192-byte fragment image per (page, head), and fp32 scales [n_pages, n_kv,
+// 2, 64], one power of two per (row, head) for K and for V.
+//
+// V image: byte (dt, kg, m, t, r) of [8][4][16][4][4] is V[row t*16 + kg*4 +
+// r][d = dt*16 + m]: lane (m, kg)'s 16 contiguous bytes of d-tile dt are the
+// 16 rows whose scores the same lane position holds after S^T = K Q^T.
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(2))) short kf8_i16x2;
+typedef __attribute__((ext_vector_type(2))) float kf8_f32x2;
+
+__device__ __forceinline__ float wave_reduce_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    v = fmaxf(v, __shfl_xor(v, off, WAVE));
+  return v;
+}
+
+// biased exponent of 2**ceil(log2(amax / 448)), floored at 2**-126: amax =
+// 1.f * 2**(e - 127) and 448 = 1.75 * 2**8, so the scale is 2**(e - 135), one
+// more when the mantissa exceeds 1.75. amax == 0 gives 1.
+__device__ __forceinline__ int kf8_scale_exp(float amax) {
+  const u32 bits = __float_as_uint(amax);
+  if (bits == 0) return 127;
+  const int sb = (int)(bits >> 23) - 8 + ((bits & 0x7fffffu) > 0x600000u);
+  return sb < 1 ? 1 : sb;
+}
+
+// Decode write: rope_cache_paged_kernel with the k and v rows quantised.
+// grid (nh + nkv, B), one wave; lane d holds the (d, d + 64) pair. Blocks
+// 0..nh-1 rope one q head. Block nh + h takes kv head h whole: it ropes k,
+// rounds it to bf16 (the value the bf16 cache would hold), reduces amax of the
+// 128 k and the 128 v values across the wave, forms the two scales, converts
+// x / scale (exact: a power of two) to e4m3fn with the hardware's round to
+// nearest even, and stores the K row (bytes meet in LDS and leave as one
+// 128-byte store), 128 V image bytes and the two scales. Vector stores only,
+// no host input: graph-capturable. Clamps as rope_cache_paged_row.
+__global__ __launch_bounds__(64) void rope_cache_paged_fp8_kernel(
+    const u16* __restrict__ qkv, u16* __restrict__ qout,
+    uint8_t* __restrict__ k8, uint8_t* __restrict__ v8,
+    float* __restrict__ sc, const float* __restrict__ inv_freq,
+    const int* __restrict__ table, const long* __restrict__ pos_dev, int nh,
+    int nkv, int n_pages, int max_pages) {
+  constexpr int D = ADEC_D, half = ADEC_D / 2;
+  const int hx = blockIdx.x;             // 0..nh-1 q, nh..nh+nkv-1 kv
+  const int b = blockIdx.y;
+  const int d = threadIdx.x;
+  long pos = pos_dev[b];
+  if (pos < 0) {
+    if (hx < nh) {
+      u16* z = qout + ((long)b * nh + hx) * D;
+      z[d] = 0;
+      z[d + half] = 0;
+    }
+    return;
+  }
+  pos = apg_clamp_pos(pos, max_pages);
+  const u16* src = qkv + ((long)b * (nh + 2 * nkv)) * D + (long)hx * D;
+  const float x1 = bf2f(src[d]), x2 = bf2f(src[d + half]);
+  float c, sn;
+  __sincosf((float)pos * inv_freq[d], &sn, &c);
+  const u16 r1 = f2bf(x1 * c - x2 * sn);
+  const u16 r2 = f2bf(x1 * sn + x2 * c);
+  if (hx < nh) {
+    u16* dst = qout + ((long)b * nh + hx) * D;
+    dst[d] = r1;
+    dst[d + half] = r2;
+    return;
+  }
+  const int hkv = hx - nh;
+  const float k1 = bf2f(r1), k2 = bf2f(r2);
+  const float v1 = bf2f(src[(long)nkv * D + d]);
+  const float v2 = bf2f(src[(long)nkv * D + d + half]);
+  const int ke = kf8_scale_exp(
+      wave_reduce_max(fmaxf(fabsf(k1), fabsf(k2))));
+  const int ve = kf8_scale_exp(
+      wave_reduce_max(fmaxf(fabsf(v1), fabsf(v2))));
+  const float kinv = __uint_as_float((u32)(254 - ke) << 23);
+  const float vinv = __uint_as_float((u32)(254 - ve) << 23);
+  kf8_i16x2 z2 = {0, 0};
+  // byte 0 = element d, byte 1 = element d + 64
+  const u32 kb = (u32)(unsigned short)__builtin_amdgcn_cvt_scalef32_pk_fp8_f32(
+      z2, k1 * kinv, k2 * kinv, 1.0f, false)[0];
+  const u32 vb = (u32)(unsigned short)__builtin_amdgcn_cvt_scalef32_pk_fp8_f32(
+      z2, v1 * vinv, v2 * vinv, 1.0f, false)[0];
+
+  const int page = apg_phys_page(table, b, max_pages, (int)(pos / APG_ROWS),
+                                 n_pages);
+  const int r = (int)(pos % APG_ROWS);
+  const long pb = (long)page * nkv + hkv;
+  __shared__ uint8_t krow[D];
+  krow[d] = (uint8_t)(kb & 0xff);
+  krow[d + half] = (uint8_t)(kb >> 8);
+  __syncthreads();
+  if (d < D / 4)
+    reinterpret_cast<u32*>(k8 + (pb * APG_ROWS + r) * D)[d] =
+        reinterpret_cast<const u32*>(krow)[d];
+  // image offset of (row r, column x): (x/16)*1024 + (kg*16 + x%16)*16 + t*4
+  // + r%4 with t = r/16, kg = (r/4)%4; d + 64 is four d-tiles further on
+  uint8_t* vd = v8 + pb * (APG_ROWS * D) + (d >> 4) * 1024
+      + (((r >> 2) & 3) * 16 + (d & 15)) * 16 + (r >> 4) * 4 + (r & 3);
+  vd[0] = (uint8_t)(vb & 0xff);
+  vd[4 * 1024] = (uint8_t)(vb >> 8);
+  if (d == 0) {
+    float* sd = sc + pb * (2 * APG_ROWS) + r;
+    sd[0] = __uint_as_float((u32)ke << 23);
+    sd[APG_ROWS] = __uint_as_float((u32)ve << 23);
+  }
+}
+
+// v of lane (lane ^ X). The kernel below carries a target attribute, and the
+// HIP headers' __shfl_xor / make_* helpers, which do not, would be CALLED
+// from it instead of inlined; builtins and vector types have no such edge.
+template <int X>
+__device__ __forceinline__ float kf8_xor_lanes(float v, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(
+      (lane ^ X) << 2, __builtin_bit_cast(int, v)));
+}
+
+// Paged decode over the fp8 pools, the partial stage: grid (n_kv, max_pages,
+// B), ONE wave per (kv head, page, slot) serving all G <= 16 q heads of the
+// group as the 16 MFMA columns, so a page is read once per kv head (the bf16
+// kernel above reads it once per q head). It writes the record attn_decode_
+// combine_kernel<true> merges: [B, n_kv, max_pages, G, 130] = acc[128], m, l.
+//
+// All 16 KB of the page (8 K loads, 8 V image loads of 16 bytes per lane, each
+// wave-wide load contiguous rows or one contiguous KB) plus the 128 scales are
+// requested before the first MFMA: one wave has nothing else to hide latency
+// with. Lane l = (n = l & 15, kg = l >> 4):
+//   S^T = K Q^T   4 row tiles x 2 k-blocks x 2 = 16 MFMAs. A: lane (row n of
+//                 the tile, kg) has 16 K bytes d = kb*64 + kg*16 + 0..15, the
+//                 two halves being the two MFMAs' fragments (gf8_cvt8); B: 32
+//                 contiguous bytes of q head n under the same k permutation,
+//                 as in gemv_fp8_kernel. Columns n >= G carry zeros.
+//   softmax       acc reg (t, r) is row t*16 + kg*4 + r of head n. The softmax
+//                 scale and the row's K scale multiply the fp32 accumulator;
+//                 rows beyond pos are replaced by select, so NaN bytes or
+//                 scales there never reach a sum. Max and sum over the lane's
+//                 16 rows, then across the 4 k-groups by two xor shuffles.
+//   O^T = V^T P^T 8 d-tiles x 2 = 16 MFMAs. B: p * V scale of the row (exact,
+//                 a power of two) rounded to bf16 straight from the registers
+//                 above; A: the image bytes, with the bytes of rows beyond pos
+//                 ANDed to zero (0 * NaN would poison the k sum).
+// Early exits as the bf16 kernel: idle slot or page beyond pos, before the
+// table is touched. Built without packed fp32 ops: see gemv_fp8_kernel.
+GEMV_NO_PK_F32 __global__ __launch_bounds__(64)
+void attn_decode_fp8_kernel(const u16* __restrict__ q,   // [B, n_kv*G, 128]
+                            const gf8_u32x4* __restrict__ k8,
+                            const gf8_u32x4* __restrict__ v8,
+                            const float* __restrict__ sc,
+                            const long* __restrict__ pos_dev,
+                            float* __restrict__ partial,
+                            int n_kv, int G, int max_pages, float scale,
+                            const int* __restrict__ table, int n_pages) {
+  const int hkv = blockIdx.x;
+  const int chunk = blockIdx.y;
+  const int b = blockIdx.z;
+  const int lane = threadIdx.x;
+  const int n = lane & 15;
+  const int kg = lane >> 4;
+  long pos = pos_dev[b];
+  if (pos < 0) return;
+  pos = apg_clamp_pos(pos, max_pages);
+  if ((long)chunk * APG_ROWS > pos) return;
+  const int page = apg_phys_page(table, b, max_pages, chunk, n_pages);
+  const long pb = (long)page * n_kv + hkv;
+  const long lim = pos + 1 - (long)chunk * APG_ROWS;
+  const int nrow = lim < APG_ROWS ? (int)lim : APG_ROWS;      // 1..64
+
+  // 16-byte units: a (page, head) block is 512 of them in either pool
+  const gf8_u32x4* kp = k8 + pb * 512 + n * 8 + kg;
+  const gf8_u32x4* vp = v8 + pb * 512 + lane;
+  gf8_u32x4 kv[4][2], vv[8];
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+      kv[t][kb] = __builtin_nontemporal_load(kp + t * 128 + kb * 4);
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt)
+    vv[dt] = __builtin_nontemporal_load(vp + dt * 64);
+  const f32x4* sp = reinterpret_cast<const f32x4*>(sc + pb * 128) + kg;
+  f32x4 ks[4], vs[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    ks[t] = sp[t * 4];
+    vs[t] = sp[16 + t * 4];
+  }
+  const bool live = n < G;
+  union { gf8_u32x4 u; bf16x8 v; } xq[2][2];
+  if (live) {
+    const gf8_u32x4* qr = reinterpret_cast<const gf8_u32x4*>(
+        q + ((long)b * n_kv * G + hkv * G + n) * ADEC_D + kg * 16);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      xq[kb][0].u = qr[kb * 8];
+      xq[kb][1].u = qr[kb * 8 + 1];
+    }
+  } else {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+      xq[kb][0].u = xq[kb][1].u = gf8_u32x4{0, 0, 0, 0};
+  }
+
+  f32x4 s[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          gf8_cvt8(kv[t][kb][0], kv[t][kb][1]), xq[kb][0].v, s[t], 0, 0, 0);
+      s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          gf8_cvt8(kv[t][kb][2], kv[t][kb][3]), xq[kb][1].v, s[t], 0, 0, 0);
+    }
+  }
+
+  float m = -1e30f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const bool valid = t * 16 + kg * 4 + r < nrow;
+      s[t][r] = valid ? s[t][r] * (scale * ks[t][r]) : -1e30f;
+      m = fmaxf(m, s[t][r]);
+    }
+  }
+  m = fmaxf(m, kf8_xor_lanes<16>(m, lane));
+  m = fmaxf(m, kf8_xor_lanes<32>(m, lane));
+
+  float l = 0.f;
+  union { bf16x8 v; u16 h[8]; } pb8[2];
+  u32 vmask[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    vmask[t] = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const bool valid = t * 16 + kg * 4 + r < nrow;
+      const float p = valid ? __expf(s[t][r] - m) : 0.f;
+      l += p;
+      pb8[t >> 1].h[(t & 1) * 4 + r] = valid ? f2bf(p * vs[t][r]) : (u16)0;
+      vmask[t] |= valid ? (0xffu << (8 * r)) : 0u;
+    }
+  }
+  l += kf8_xor_lanes<16>(l, lane);
+  l += kf8_xor_lanes<32>(l, lane);
+
+  float* out = partial
+      + ((((long)b * n_kv + hkv) * max_pages + chunk) * G + n) * (ADEC_D + 2);
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) {
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+        gf8_cvt8(vv[dt][0] & vmask[0], vv[dt][1] & vmask[1]), pb8[0].v, o,
+        0, 0, 0);
+    o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+        gf8_cvt8(vv[dt][2] & vmask[2], vv[dt][3] & vmask[3]), pb8[1].v, o,
+        0, 0, 0);
+    if (live) {          // O^T[d = dt*16 + kg*4 + r][head n]; rows are 520 B
+      kf8_f32x2* od = reinterpret_cast<kf8_f32x2*>(out + dt * 16 + kg * 4);
+      od[0] = kf8_f32x2{o[0], o[1]};
+      od[1] = kf8_f32x2{o[2], o[3]};
+    }
+  }
+  if (live && kg == 0) {
+    out[ADEC_D] = m;
+    out[ADEC_D + 1] = l;
+  }
+}
+
+
+// ---------------------------------------------------------------------------
 // Indirect (routed) decode GEMV for MoE: the expert id comes from a
 // DEVICE tensor and the weight base from a device-resident pointer
 // table, so b1 decode routing never synchronizes to the host (the
@@ -2258,6 +2533,53 @@ int rope_cache_paged_rows(void* stream, const void* qkv, void* qout,
                      (const int*)block_table, (const int*)tok_slot,
                      (const long*)tok_pos, B, nh, nkv, n_pages, max_pages,
                      D);
+  return 0;
+}
+
+
+// fp8 KV cache, decode write (rope_cache_paged_fp8_kernel): rope_cache_paged
+// with k8/v8 uint8 pools [n_pages, nkv, 64, 128] (v8: fragment images) and
+// sc fp32 [n_pages, nkv, 2, 64]. D is 128.
+int rope_cache_paged_fp8(void* stream, const void* qkv, void* qout, void* k8,
+                         void* v8, void* sc, const void* inv_freq,
+                         const void* block_table, const void* pos_dev, int B,
+                         int nh, int nkv, int n_pages, int max_pages) {
+  if (nh <= 0 || nkv <= 0 || B <= 0 || B > 65535 || n_pages <= 0 ||
+      max_pages <= 0 || !qkv || !qout || !k8 || !v8 || !sc || !inv_freq ||
+      !block_table || !pos_dev)
+    return -1;
+  dim3 grid((unsigned)(nh + nkv), (unsigned)B);
+  hipLaunchKernelGGL(rope_cache_paged_fp8_kernel, grid, dim3(64), 0, STREAM,
+                     (const u16*)qkv, (u16*)qout, (uint8_t*)k8, (uint8_t*)v8,
+                     (float*)sc, (const float*)inv_freq,
+                     (const int*)block_table, (const long*)pos_dev, nh, nkv,
+                     n_pages, max_pages);
+  return 0;
+}
+
+// fp8 KV cache, paged decode attention (attn_decode_fp8_kernel + the bf16
+// route's combine): attn_decode_paged's arguments with the three fp8 pools.
+// G = H / n_kv <= 16 (the MFMA's columns).
+int attn_decode_paged_fp8(void* stream, const void* q, const void* k8,
+                          const void* v8, const void* sc,
+                          const void* block_table, const void* pos_dev,
+                          void* partial, void* o, int B, int H, int n_kv,
+                          int n_pages, int max_pages, float scale) {
+  if (B <= 0 || B > 65535 || n_kv <= 0 || H <= 0 || H % n_kv != 0 ||
+      H / n_kv > 16 || n_pages <= 0 || max_pages <= 0 || max_pages > 65535 ||
+      !q || !k8 || !v8 || !sc || !block_table || !pos_dev || !partial || !o)
+    return -1;
+  const int G = H / n_kv;
+  dim3 grid((unsigned)n_kv, (unsigned)max_pages, (unsigned)B);
+  hipLaunchKernelGGL(attn_decode_fp8_kernel, grid, dim3(64), 0, STREAM,
+                     (const u16*)q, (const gf8_u32x4*)k8,
+                     (const gf8_u32x4*)v8, (const float*)sc,
+                     (const long*)pos_dev, (float*)partial, n_kv, G,
+                     max_pages, scale, (const int*)block_table, n_pages);
+  hipLaunchKernelGGL(attn_decode_combine_kernel<true>,
+                     dim3((unsigned)(B * H)), dim3(128), 0, STREAM,
+                     (const float*)partial, (u16*)o, n_kv, G, max_pages,
+                     (const long*)pos_dev);
   return 0;
 }
 

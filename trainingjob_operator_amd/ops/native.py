@@ -90,6 +90,12 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # n_pages, max_pages, D)
     _sig(lib.rope_cache_paged, [vp, vp, vp, vp, vp, vp, vp, vp,
                                 i, i, i, i, i, i], i)
+    # fp8 KV cache (format: reference.py): the two calls above with the
+    # uint8 k8 / v8-image pools and the fp32 scale pool in place of k/v
+    _sig(lib.attn_decode_paged_fp8, [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    i, i, i, i, i, f], i)
+    _sig(lib.rope_cache_paged_fp8, [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   i, i, i, i, i], i)
     # paged prefill: (qkv, qout, k_pool, v_pool, inv_freq, block_table,
     # tok_slot int32 [T], tok_pos int64 [T], T, B, nh, nkv, n_pages,
     # max_pages, D)

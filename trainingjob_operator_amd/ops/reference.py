@@ -204,6 +204,153 @@ def rope_cache_paged_rows(qkv: torch.Tensor, k_pool: torch.Tensor,
                             num_kv_heads)
 
 
+# ---------------------------------------------------------------------------
+# fp8 KV cache: THE definition of the format; the kernels (hip/ops.hip
+# rope_cache_paged_fp8_kernel, attn_decode_fp8_kernel) reproduce it byte for
+# byte. Per layer three pools:
+#   k8 [n_pages, n_kv, 64, 128] uint8  e4m3fn, row-major: a token's K row
+#                                      (after RoPE) is 128 contiguous bytes
+#   v8 [n_pages, n_kv, 64, 128] uint8  e4m3fn, each (page, head) block an
+#                                      8192-byte fragment image, see below
+#   sc [n_pages, n_kv, 2, 64]   fp32   one scale per (row, head): [0] K, [1] V
+# 132 bytes per (row, head, K or V) against bf16's 256. The scale is the
+# power of two 2**ceil(log2(amax / 448)) of the row's 128 values (amax == 0
+# gives 1), so x / scale is exact, the conversion rounds once (to nearest
+# even, subnormals kept) and nothing overflows. The exponent is floored at
+# -126 so that the scale and its reciprocal stay normal fp32 numbers.
+#
+# V image of one (page, head): byte (dt, kg, m, t, r) of a [8, 4, 16, 4, 4]
+# block is V[row t*16 + kg*4 + r][d = dt*16 + m]. The decode kernel computes
+# S^T = K Q^T with 16x16x32 MFMAs, after which lane (n, kg) holds the scores
+# of exactly the rows t*16 + kg*4 + r; lane (m, kg)'s 16 contiguous image
+# bytes of d-tile dt are those rows of column d, i.e. its A operand of
+# O^T = V^T P^T, so P goes from the accumulator straight into the B operand.
+# ---------------------------------------------------------------------------
+
+KV_FP8_MAX = 448.0
+
+
+def _kv_fp8_scale(amax: torch.Tensor) -> torch.Tensor:
+    """2**ceil(log2(amax / 448)) from the exponent of amax (no division and
+    no log to round): amax = m * 2**e with m in [0.5, 1), 448 = 0.875 * 2**9."""
+    mant, exp = torch.frexp(amax.float())
+    e = (exp - 9 + (mant > 0.875).to(exp.dtype)).clamp(min=-126)
+    scale = torch.ldexp(torch.ones_like(mant), e)
+    return torch.where(amax > 0, scale, torch.ones_like(scale))
+
+
+def kv_fp8_quant_rows(k: torch.Tensor, v: torch.Tensor
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """k, v [..., 128] rows (k after RoPE) -> (k8, v8, scales): uint8
+    [..., 128] e4m3fn bytes in d order and fp32 [..., 2] (K scale, V scale).
+    k8 rows are the K pool's rows as they stand; the bytes of a v8 row go
+    to the image offsets kv_fp8_v_offsets(row) of its (page, head)."""
+    out = []
+    for x in (k, v):
+        xf = x.float()
+        scale = _kv_fp8_scale(xf.abs().amax(dim=-1))
+        q = (xf / scale[..., None]).clamp(-KV_FP8_MAX, KV_FP8_MAX)
+        out.append((q.to(torch.float8_e4m3fn).view(torch.uint8), scale))
+    (k8, ks), (v8, vs) = out
+    return k8, v8, torch.stack([ks, vs], dim=-1)
+
+
+def kv_fp8_v_offsets(row: torch.Tensor) -> torch.Tensor:
+    """Byte offsets [..., 128] (one per d) of page row `row` (0..63, long)
+    inside the 8192-byte V image of its (page, head)."""
+    d = torch.arange(128, device=row.device)
+    row = row.long()[..., None]
+    return ((d // 16) * 1024 + (((row >> 2) & 3) * 16 + d % 16) * 16
+            + (row >> 4) * 4 + (row & 3))
+
+
+def kv_fp8_v_image(v8: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+    """[..., 64, 128] row-major V bytes -> the fragment image of the same
+    shape (whole pages at once); inverse=True goes back."""
+    lead = v8.shape[:-2]
+    n = len(lead)
+    if inverse:     # [dt, kg, m, t, r] -> [t, kg, r, dt, m]
+        x = v8.reshape(*lead, 8, 4, 16, 4, 4).permute(
+            *range(n), n + 3, n + 1, n + 4, n + 0, n + 2)
+    else:           # [t, kg, r, dt, m] -> [dt, kg, m, t, r]
+        x = v8.reshape(*lead, 4, 4, 4, 8, 16).permute(
+            *range(n), n + 3, n + 1, n + 4, n + 0, n + 2)
+    return x.reshape(*lead, 64, 128)
+
+
+def kv_fp8_quant_pages(k: torch.Tensor, v: torch.Tensor):
+    """Whole pages k, v [..., n_kv, 64, 128] -> (k8, v8 image, sc [..., n_kv,
+    2, 64]): what writing the 64 rows one at a time leaves behind."""
+    k8, v8, sc = kv_fp8_quant_rows(k, v)
+    return k8, kv_fp8_v_image(v8), sc.transpose(-1, -2).contiguous()
+
+
+def kv_fp8_write_rows(k8_pool: torch.Tensor, v8_pool: torch.Tensor,
+                      sc_pool: torch.Tensor, page: torch.Tensor,
+                      row: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor,
+                      sc: torch.Tensor) -> None:
+    """Store N quantised rows (k8, v8 [N, n_kv, 128], sc [N, n_kv, 2]) at
+    (page[n], row[n]) of the pools, in place."""
+    n_kv = k8_pool.shape[1]
+    k8_pool[page, :, row] = k8
+    off = kv_fp8_v_offsets(row)[:, None, :].expand(-1, n_kv, -1)   # [N,kv,128]
+    flat = v8_pool.view(v8_pool.shape[0], n_kv, 64 * 128)
+    flat[page[:, None, None], torch.arange(n_kv, device=page.device)[None, :,
+                                                                     None],
+         off] = v8
+    sc_pool[page, :, :, row] = sc
+
+
+def kv_fp8_dequant(k8_pool: torch.Tensor, v8_pool: torch.Tensor,
+                   sc_pool: torch.Tensor, dtype=torch.bfloat16
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The pools as row-major [n_pages, n_kv, 64, 128] K and V of `dtype`.
+    value * scale has 4 significant bits, so bf16 holds it exactly."""
+    k = k8_pool.view(torch.float8_e4m3fn).float() * sc_pool[:, :, 0, :, None]
+    v = kv_fp8_v_image(v8_pool, inverse=True).contiguous().view(
+        torch.float8_e4m3fn).float() * sc_pool[:, :, 1, :, None]
+    return k.to(dtype), v.to(dtype)
+
+
+def rope_cache_paged_fp8(qkv: torch.Tensor, k8_pool: torch.Tensor,
+                         v8_pool: torch.Tensor, sc_pool: torch.Tensor,
+                         inv_freq: torch.Tensor, block_table: torch.Tensor,
+                         pos: torch.Tensor, num_heads: int,
+                         num_kv_heads: int) -> torch.Tensor:
+    """Twin of rope_cache_paged_fp8: rope_cache_paged whose k (roped, rounded
+    to qkv.dtype) and v rows are quantised (kv_fp8_quant_rows) into the fp8
+    pools, in place. Returns q [B, nh, D]; an idle slot writes nothing."""
+    n_pages, _, R, D = k8_pool.shape
+    B = qkv.shape[0]
+    # one scratch page per slot: the bf16 twin ropes and places the rows
+    tk = torch.zeros(B, num_kv_heads, R, D, dtype=qkv.dtype,
+                     device=qkv.device)
+    tv = torch.zeros_like(tk)
+    own = torch.arange(B, dtype=torch.int32, device=block_table.device
+                       )[:, None].expand(B, block_table.shape[1])
+    q = rope_cache_paged(qkv, tk, tv, inv_freq, own, pos, num_heads,
+                         num_kv_heads)
+    pos = pos.to(qkv.device)
+    act = (pos >= 0).nonzero().squeeze(1)
+    if act.numel():
+        p = pos[act].clamp(0, block_table.shape[1] * R - 1)
+        page = block_table.long()[act, p // R].clamp(0, n_pages - 1)
+        row = p % R
+        k8, v8, sc = kv_fp8_quant_rows(tk[act, :, row], tv[act, :, row])
+        kv_fp8_write_rows(k8_pool, v8_pool, sc_pool, page, row, k8, v8, sc)
+    return q
+
+
+def decode_attention_paged_fp8(q: torch.Tensor, k8_pool: torch.Tensor,
+                               v8_pool: torch.Tensor, sc_pool: torch.Tensor,
+                               block_table: torch.Tensor, pos: torch.Tensor,
+                               scale: float) -> torch.Tensor:
+    """Twin of attn_decode_paged_fp8: decode_attention_paged over the
+    dequantised pools (in q.dtype)."""
+    k, v = kv_fp8_dequant(k8_pool, v8_pool, sc_pool, q.dtype)
+    return decode_attention_paged(q, k, v, block_table, pos, scale)
+
+
 PREFILL_BLOCK_ROWS = 256    # q rows of one work-list block (the v7 tile)
 
 
