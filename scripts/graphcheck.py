@@ -6,6 +6,7 @@ large training step on ROCm 7.2, so the graph path is exercised here, not
 in the driver-run GPU suite.
 
   python scripts/graphcheck.py            # correctness on llama-smoke
+  python scripts/graphcheck.py --weights fp8   # the same over fp8 weights
   python scripts/graphcheck.py bench      # llama3-8b b1/b8 decode tok/s
   python scripts/graphcheck.py --paged    # captured paged engine step
 """
@@ -37,7 +38,7 @@ def tokens_per_sec(model, batch, prompt_len, new_tokens):
     return batch * new_tokens / dt, dt * 1e3 / new_tokens
 
 
-def check():
+def check(weights="bf16"):
     from trainingjob_operator_amd.models.config import CONFIGS
     from trainingjob_operator_amd.models.generate import (
         build_inference_model, generate,
@@ -49,12 +50,12 @@ def check():
         prompt = torch.randint(0, cfg.vocab_size, (2, 16),
                                generator=g).to("cuda:0")
         os.environ["AITJ_DECODE_GRAPH"] = "0"
-        ref = generate(m, prompt, max_new_tokens=24)
+        ref = generate(m, prompt, max_new_tokens=24, weights=weights)
         os.environ["AITJ_DECODE_GRAPH"] = "1"
-        got = generate(m, prompt, max_new_tokens=24)
+        got = generate(m, prompt, max_new_tokens=24, weights=weights)
         match = (ref == got).float().mean().item()
-        print(f"{name}: token agreement graph vs eager: {match:.3f} "
-              f"({ref.shape[1]} positions)")
+        print(f"{name} ({weights} weights): token agreement graph vs eager: "
+              f"{match:.3f} ({ref.shape[1]} positions)")
         assert match > 0.95, (name, ref, got)
         del m
         torch.cuda.empty_cache()
@@ -159,5 +160,7 @@ if __name__ == "__main__":
         bench()
     elif len(sys.argv) > 1 and sys.argv[1] == "session":
         session()
+    elif "--weights" in sys.argv[1:]:
+        check(sys.argv[sys.argv.index("--weights") + 1])
     else:
         check()

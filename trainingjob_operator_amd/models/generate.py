@@ -25,6 +25,8 @@ import torch
 from ..ops import (decode_linear, decode_linear_fp8, decode_swiglu,
                    decode_swiglu_fp8, fused_rmsnorm, swiglu_packed)
 from ..ops.fp8_weight import quantize_rows
+from ..parallel.ep import expert_fp8, quantize_expert
+from ..parallel.tp import _group_size
 from .config import LlamaConfig
 from .llama import LlamaModel, _sdpa
 
@@ -56,13 +58,17 @@ def quantize_decode_weights(model) -> int:
     powers of two, so the write-back is exact in bf16: prefill, steps of
     more than 16 rows and the bf16 GEMVs then compute the same model as the
     fp8 GEMVs. The bf16 weights stay resident (this halves the bytes a
-    decode step streams, not the model's footprint). MoE experts, the
-    embedding (and an lm_head tied to it) and the norms are untouched, and
-    so is a weight whose shape the kernel does not take. An fp8_weight
-    remembers the version of the weight it was made from: after the weight
+    decode step streams, not the model's footprint). Every expert of an MoE
+    block that is not sharded (no EP or TP group) is quantised the same way
+    (parallel/ep.py quantize_expert): gate and up together as one packed
+    gate|up weight, down plain, written back exactly, for the routed fp8
+    GEMVs of MoEMLP._decode_forward. The router, the embedding (and an
+    lm_head tied to it) and the norms are untouched, and so is a weight (or
+    an expert) whose shape the kernel does not take. An fp8 weight
+    remembers the version of the weight(s) it was made from: after a weight
     is written again (load_state_dict, an optimizer step) it is no longer
     used, and the next call here replaces it. Returns the number of weights
-    that now carry one."""
+    that now carry one; an expert counts as two (gate|up and down)."""
     mods = []
     for blk in model.blocks:
         mods += [(blk.attn.qkv_proj, False), (blk.attn.o_proj, False)]
@@ -73,6 +79,14 @@ def quantize_decode_weights(model) -> int:
         mods.append((model.lm_head, False))
     done = 0
     with torch.no_grad():
+        for blk in model.blocks:
+            moe = getattr(blk, "moe", None)
+            if moe is None or moe.tp_group is not None or \
+                    _group_size(moe.group) != 1:
+                continue
+            for ex in moe.experts:
+                if expert_fp8(ex) is not None or quantize_expert(ex):
+                    done += 2
         for mod, gate_up in mods:
             if _fp8_weight(mod) is None:
                 w8 = quantize_rows(mod.weight, gate_up=gate_up)
@@ -278,7 +292,7 @@ def _layers_cached(model, x: torch.Tensor, attend, fp8: bool = False):
         # topk -> pointer-table GEMVs, fixed shapes, no host syncs), so MoE
         # blocks are stream-capturable too
         x = _mlp_cached(blk.mlp, normed, fp8) if hasattr(blk, "mlp") \
-            else blk.moe(normed)
+            else blk.moe(normed, fp8)
     return x, residual
 
 
@@ -317,7 +331,7 @@ def _forward_cached(model: LlamaModel, tokens: torch.Tensor,
         # dense blocks carry .mlp; MoE blocks carry .moe (routing works
         # per token, so single-token decode steps route normally)
         x = _mlp_cached(blk.mlp, normed, fp8) if hasattr(blk, "mlp") \
-            else blk.moe(normed)
+            else blk.moe(normed, fp8)
     cache.len = pos0 + tokens.shape[1]
     normed, _ = fused_rmsnorm(x, model.final_norm_weight, residual,
                               cfg.norm_eps)

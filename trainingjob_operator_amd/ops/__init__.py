@@ -12,6 +12,8 @@ from .functional import (
     decode_attention_paged_fp8,
     decode_linear,
     decode_linear_fp8,
+    decode_moe_fp8,
+    decode_moe_swiglu_fp8,
     decode_swiglu,
     decode_swiglu_fp8,
     fused_cross_entropy,
@@ -38,6 +40,8 @@ __all__ = [
     "decode_attention_paged_fp8",
     "decode_linear",
     "decode_linear_fp8",
+    "decode_moe_fp8",
+    "decode_moe_swiglu_fp8",
     "decode_swiglu",
     "decode_swiglu_fp8",
     "dispatch_rows",

@@ -17,7 +17,7 @@ its A operands of two 16x16x32 MFMAs. A gate|up weight [2F, K] is packed as
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -60,6 +60,35 @@ class Fp8Weight:
             q = _unpack(p)
         q = q.contiguous().view(torch.float8_e4m3fn).float()
         return q * self.scale[:, None].to(q.device)
+
+
+@dataclass
+class Fp8ExpertTables:
+    """What the routed fp8 GEMVs (hip/ops.hip gemv_moe_fp8_kernel) read for
+    one weight of every expert of an MoE layer: device int64 [E] tables of
+    the experts' packed bytes and of their scales. The Fp8Weights are held
+    here so that the pointers stay valid as long as the tables do."""
+    experts: List[Fp8Weight]
+    w: torch.Tensor               # int64 [E]: packed.data_ptr()
+    s: torch.Tensor               # int64 [E]: scale.data_ptr()
+    M: int
+    K: int
+    gate_up: bool
+
+
+def expert_tables(experts: List[Fp8Weight]) -> Fp8ExpertTables:
+    """Tables over same-shaped Fp8Weights living on one device."""
+    e0 = experts[0]
+    assert all((e.M, e.K, e.gate_up) == (e0.M, e0.K, e0.gate_up)
+               and e.packed.device == e0.packed.device
+               and e.packed.is_contiguous() and e.scale.is_contiguous()
+               for e in experts)
+    dev = e0.packed.device
+    w = torch.tensor([e.packed.data_ptr() for e in experts],
+                     dtype=torch.int64, device=dev)
+    s = torch.tensor([e.scale.data_ptr() for e in experts],
+                     dtype=torch.int64, device=dev)
+    return Fp8ExpertTables(list(experts), w, s, e0.M, e0.K, e0.gate_up)
 
 
 def quantize_rows(weight: torch.Tensor,

@@ -687,6 +687,51 @@ def decode_swiglu_fp8(x: torch.Tensor, gu8) -> Optional[torch.Tensor]:
     return y.reshape(*x.shape[:-1], F)
 
 
+def _moe_fp8(swiglu: bool, x, idx, tables, M: int, K: int, xdiv: int):
+    """The routed fp8 GEMVs' shared front: None unless everything is on the
+    GPU and (x, idx, tables) is a call the kernel takes."""
+    N = idx.numel()
+    rows_w = 2 * M if swiglu else M
+    if not (x.is_cuda and idx.is_cuda and x.dtype == torch.bfloat16
+            and idx.dtype == torch.int64 and x.dim() == 2 and idx.dim() == 1
+            and 1 <= N <= 16 and xdiv >= 1 and x.shape[1] == K
+            and x.shape[0] * xdiv >= N and tables.gate_up == swiglu
+            and (tables.M, tables.K) == (rows_w, K)
+            and tables.w.device == x.device and M % 16 == 0
+            and K % 512 == 0 and 1 <= len(tables.experts) <= 65535):
+        return None
+    xc, ic = x.contiguous(), idx.contiguous()
+    y = torch.empty(N, M, dtype=torch.bfloat16, device=x.device)
+    lib = _hip()
+    fn = lib.gemv_moe_fp8_swiglu if swiglu else lib.gemv_moe_fp8
+    rc = fn(native.stream_ptr(), _ptr(tables.w), _ptr(tables.s), _ptr(ic),
+            _ptr(xc), _ptr(y), M, K, N, len(tables.experts), xdiv)
+    native.check_rc(rc, "gemv_moe_fp8_swiglu" if swiglu else "gemv_moe_fp8",
+                    f"M={M} K={K} N={N} xdiv={xdiv}")
+    return y
+
+
+def decode_moe_fp8(x: torch.Tensor, idx: torch.Tensor, tables, M: int,
+                   K: int, xdiv: int) -> Optional[torch.Tensor]:
+    """Routed decode GEMV over e4m3 experts, expert-grouped on the matrix
+    cores (hip/ops.hip gemv_moe_fp8): y[n] = x[n // xdiv] @ dequant(expert
+    idx[n])^T for the N = idx.numel() <= 16 routed pairs, [N, M] bf16. idx is
+    a device int64 tensor and is never read on the host; tables is the
+    Fp8ExpertTables (ops/fp8_weight.py) of the experts' plain [M, K] weights.
+    A hit expert is streamed once, however many pairs it serves; an unhit
+    one is not read. A pair whose index is outside [0, E) gets no output:
+    its row of y stays as torch.empty left it. Returns None off the GPU or
+    for a call the kernel does not take. Inference-only."""
+    return _moe_fp8(False, x, idx, tables, M, K, xdiv)
+
+
+def decode_moe_swiglu_fp8(x: torch.Tensor, idx: torch.Tensor, tables, F: int,
+                          K: int, xdiv: int) -> Optional[torch.Tensor]:
+    """decode_moe_fp8 over the experts' packed gate|up [2F, K] weights with
+    silu(gate) * up in the epilogue (gemv_moe_fp8_swiglu): [N, F] bf16."""
+    return _moe_fp8(True, x, idx, tables, F, K, xdiv)
+
+
 # ---------------------------------------------------------------------------
 # Fused cross-entropy
 # ---------------------------------------------------------------------------

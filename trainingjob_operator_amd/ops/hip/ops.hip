@@ -1609,6 +1609,143 @@ void gemv_fp8_kernel(const gf8_u32x4* __restrict__ w8,
 
 
 // ---------------------------------------------------------------------------
+// Routed (MoE) fp8 decode GEMV, expert-grouped: the 16 MFMA columns are the
+// routed (token, k) pairs n < N <= 16 and the grid is (M/16 tiles, E experts).
+// Workgroup (tile, e) is SPLIT waves on one 16-row tile of expert e's packed
+// weight (the layout above; NW = 2 for gate|up); column n is live iff
+// idx[n] == e, so one pass over the tile serves every pair routed to e and
+// the bytes streamed per call are (distinct experts hit) x (expert bytes),
+// where the bf16 routed kernels below stream (pairs) x (expert bytes in bf16).
+//
+//   gemv_moe_fp8_swiglu: y[n] = silu(Wg[e_n] @ x[n / xdiv]) * (Wu[e_n] @ ..)
+//   gemv_moe_fp8:        y[n] = W[e_n] @ x[n / xdiv]
+//
+// idx is the router's device int64 topk; table_w / table_s are device u64
+// arrays, one entry per expert, of the packed bytes and the fp32 row scales.
+// An index is only ever COMPARED with the workgroup's own expert id, never
+// added to a pointer: a pair whose index lies outside [0, E) is live nowhere
+// and its output row is left unwritten. A workgroup with no live column (the
+// ballot is the same in all its waves: liveness depends on lane & 15 alone)
+// returns before it reads either table, so an expert nobody routed to costs
+// a launch slot and 16 index loads, not a byte of weight.
+//
+// k loop and epilogue are gemv_fp8_kernel's - chunk c belongs to wave c %
+// SPLIT with SPLIT = gemv_fp8_split(M / 16, K) of ONE expert, partial tiles
+// meet in LDS and are added in wave order, then scale, silu(gate) * up, round
+// - and an MFMA column's value depends on that column of B alone: pair n's
+// row is the bits of a one-row gemv_fp8 over its expert, whatever the other
+// pairs are routed to. Reads nothing but shapes from the host; vector stores
+// only; no calls (builtins and ext-vector types, see gemv_fp8_kernel on the
+// packed fp32 ops).
+// ---------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(2))) unsigned int gf8_u32x2;
+typedef __attribute__((address_space(1))) gf8_u32x4 gf8_global_u32x4;
+typedef __attribute__((address_space(1))) float gf8_global_f32;
+
+template <int SPLIT, bool SWIGLU>
+GEMV_NO_PK_F32 __global__ __launch_bounds__(64 * SPLIT)
+void gemv_moe_fp8_kernel(const unsigned long long* __restrict__ table_w,
+                         const unsigned long long* __restrict__ table_s,
+                         const long* __restrict__ idx,
+                         const u16* __restrict__ x, u16* __restrict__ y,
+                         int M, int K, int N, int xdiv) {
+  constexpr int NW = SWIGLU ? 2 : 1;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int n = lane & 15;             // routed pair column
+  const int kg = lane >> 4;            // k group of the fragments
+  const int tile = blockIdx.x;
+  const int e = blockIdx.y;
+  const int kb = K >> 6;               // k-blocks per row
+  const bool live = n < N && idx[n < N ? n : 0] == (long)e;
+  if (__builtin_amdgcn_ballot_w64(live) == 0) return;   // expert not hit
+
+  // table entries are device (global) addresses: say so, or the loads
+  // through them become flat loads
+  const gf8_global_u32x4* wt = (const gf8_global_u32x4*)table_w[e] +
+                               (long)tile * NW * kb * 64 + lane;
+  const gf8_global_f32* scale = (const gf8_global_f32*)table_s[e];
+  // 16-byte pieces of pair n's x row from this lane's k offset; dead lanes
+  // load nothing (their pointer stays on row 0 and is not followed)
+  const gf8_u32x4* xr = reinterpret_cast<const gf8_u32x4*>(
+      x + (long)(live ? n / xdiv : 0) * K + kg * 16);
+  f32x4 acc[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int c = wave; c < K / GF8_CHUNK; c += SPLIT) {
+    gf8_u32x4 wv[NW][8];
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+        wv[j][b] = __builtin_nontemporal_load(
+            wt + ((long)j * kb + c * 8 + b) * 64);
+    union { gf8_u32x4 u; bf16x8 v; } xv[8][2];
+    if (live) {
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        xv[b][0].u = xr[c * (GF8_CHUNK / 8) + b * 8];
+        xv[b][1].u = xr[c * (GF8_CHUNK / 8) + b * 8 + 1];
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+        xv[b][0].u = xv[b][1].u = gf8_u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gf8_cvt8(wv[j][b][0], wv[j][b][1]), xv[b][0].v, acc[j], 0, 0, 0);
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            gf8_cvt8(wv[j][b][2], wv[j][b][3]), xv[b][1].v, acc[j], 0, 0, 0);
+      }
+  }
+
+  if constexpr (SPLIT > 1) {
+    // partial tiles [wave][NW][4 regs][64 lanes]; wave 0 adds in wave order
+    __shared__ float red[SPLIT * NW * 4 * 64];
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        red[((wave * NW + j) * 4 + r) * 64 + lane] = acc[j][r];
+    // __syncthreads() by its builtins: the header's function would be a call
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (wave != 0) return;
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float s = red[(j * 4 + r) * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < SPLIT; ++w)
+          s += red[((w * NW + j) * 4 + r) * 64 + lane];
+        acc[j][r] = s;
+      }
+  }
+  if (!live) return;
+  // lane holds C[m0 + r][n], r = 0..3: four adjacent bf16 of y row n
+  const int m0 = tile * 16 + kg * 4;
+  union { gf8_u32x2 u; u16 h[4]; } out;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float v = acc[0][r] * scale[m0 + r];
+    if (SWIGLU) {
+      const float up = acc[1][r] * scale[M + m0 + r];
+      v = v / (1.f + expf(-v)) * up;             // silu(gate) * up
+    }
+    out.h[r] = f2bf(v);
+  }
+  *reinterpret_cast<gf8_u32x2*>(y + (long)n * M + m0) = out.u;
+}
+
+
+// ---------------------------------------------------------------------------
 // fp8 KV cache (format: ops/reference.py "fp8 KV cache", the torch twin these
 // two kernels reproduce byte for byte). Per layer a K byte pool [n_pages,
 // n_kv, 64, 128] row-major, a V byte pool of the same size holding one
@@ -2651,6 +2788,54 @@ int gemv_fp8(void* stream, const void* w8, const void* scale, const void* x,
 int gemv_fp8_swiglu(void* stream, const void* w8, const void* scale,
                     const void* x, void* y, int F, int K, int N) {
   return gemv_fp8_launch(true, stream, w8, scale, x, y, F, K, N);
+}
+
+// Routed fp8 decode GEMVs (gemv_moe_fp8_kernel): grid (tiles, E), the split
+// of ONE expert's tiles, so chunk owners and addition order are gemv_fp8's.
+static int gemv_moe_fp8_launch(bool swiglu, void* stream, const void* table_w,
+                               const void* table_s, const void* idx,
+                               const void* x, void* y, int M, int K, int N,
+                               int E, int xdiv) {
+  if (M <= 0 || K <= 0 || (M % 16) != 0 || (K % GF8_CHUNK) != 0 || N < 1 ||
+      N > 16 || E < 1 || E > 65535 || xdiv < 1 || !table_w || !table_s ||
+      !idx || !x || !y)
+    return -1;
+  const int tiles = M / 16;
+  dim3 grid((unsigned)tiles, (unsigned)E);
+  switch (gemv_fp8_split(tiles, K)) {
+#define GMF8_LAUNCH(S, SW) \
+    hipLaunchKernelGGL((gemv_moe_fp8_kernel<S, SW>), grid, dim3(64 * S), 0, \
+                       STREAM, (const unsigned long long*)table_w, \
+                       (const unsigned long long*)table_s, (const long*)idx, \
+                       (const u16*)x, (u16*)y, M, K, N, xdiv)
+#define GMF8_CASE(S) \
+    case S: \
+      if (swiglu) GMF8_LAUNCH(S, true); else GMF8_LAUNCH(S, false); \
+      break;
+    GMF8_CASE(1) GMF8_CASE(2) GMF8_CASE(4) GMF8_CASE(8)
+#undef GMF8_CASE
+#undef GMF8_LAUNCH
+  }
+  return 0;
+}
+
+// table_w / table_s: device u64 [E] of each expert's packed [M, K] weight and
+// fp32 [M] scales; idx device int64 [N]; x bf16 [ceil(N / xdiv), K]; y bf16
+// [N, M]. Pair n reads x row n / xdiv. Rows whose idx is outside [0, E) are
+// not written.
+int gemv_moe_fp8(void* stream, const void* table_w, const void* table_s,
+                 const void* idx, const void* x, void* y, int M, int K, int N,
+                 int E, int xdiv) {
+  return gemv_moe_fp8_launch(false, stream, table_w, table_s, idx, x, y, M,
+                             K, N, E, xdiv);
+}
+
+// the packed gate|up [2F, K] experts (scales fp32 [2F]) -> y [N, F]
+int gemv_moe_fp8_swiglu(void* stream, const void* table_w,
+                        const void* table_s, const void* idx, const void* x,
+                        void* y, int F, int K, int N, int E, int xdiv) {
+  return gemv_moe_fp8_launch(true, stream, table_w, table_s, idx, x, y, F,
+                             K, N, E, xdiv);
 }
 
 

@@ -79,6 +79,10 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.gemv_fp8_split, [i, i], i)
     _sig(lib.gemv_moe_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i], i)
     _sig(lib.gemv_moe, [vp, vp, vp, vp, vp, i, i, i, i], i)
+    # routed fp8 GEMVs, expert-grouped: (u64 table of packed weights, u64
+    # table of scales, idx int64 [N], x, y, M | F, K, N <= 16, E, xdiv)
+    _sig(lib.gemv_moe_fp8, [vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
+    _sig(lib.gemv_moe_fp8_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
     _sig(lib.attn_decode, [vp, vp, vp, vp, vp, vp, vp,
                            i, i, i, i, i, f], i)
     _sig(lib.rope_cache, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)

@@ -591,3 +591,24 @@ def decode_swiglu_fp8(x: torch.Tensor, gu8) -> torch.Tensor:
     gu = x.float() @ gu8.dequant().to(x.device).t()
     g, u = gu.chunk(2, dim=-1)
     return (torch.nn.functional.silu(g) * u).to(x.dtype)
+
+
+def _moe_fp8(one, x, idx, tables, xdiv):
+    rows = [one(x[n // xdiv][None], tables.experts[e])
+            for n, e in enumerate(idx.tolist())]
+    return torch.cat(rows)
+
+
+def decode_moe_fp8(x: torch.Tensor, idx: torch.Tensor, tables, M: int,
+                   K: int, xdiv: int) -> torch.Tensor:
+    """Twin of hip/ops.hip gemv_moe_fp8: pair n is decode_linear_fp8 of x row
+    n // xdiv over expert idx[n]'s Fp8Weight (reads idx on the host)."""
+    assert (tables.M, tables.K, tables.gate_up) == (M, K, False)
+    return _moe_fp8(decode_linear_fp8, x, idx, tables, xdiv)
+
+
+def decode_moe_swiglu_fp8(x: torch.Tensor, idx: torch.Tensor, tables, F: int,
+                          K: int, xdiv: int) -> torch.Tensor:
+    """Twin of gemv_moe_fp8_swiglu over the experts' gate|up weights."""
+    assert (tables.M, tables.K, tables.gate_up) == (2 * F, K, True)
+    return _moe_fp8(decode_swiglu_fp8, x, idx, tables, xdiv)

@@ -21,7 +21,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ..ops import swiglu
+from ..ops import decode_moe_fp8, decode_moe_swiglu_fp8, swiglu
+from ..ops.fp8_weight import expert_tables, quantize_rows
 from .tp import _group_size
 
 
@@ -109,6 +110,43 @@ class Expert(nn.Module):
                                      self.up_proj(x).contiguous()))
 
 
+def _expert_weights(ex):
+    return (ex.gate_proj.weight, ex.up_proj.weight, ex.down_proj.weight)
+
+
+def expert_fp8(ex):
+    """An expert's (gate|up, down) Fp8Weights, unless it has none or one of
+    its three weights was written since they were made."""
+    w8 = getattr(ex, "fp8_weights", None)
+    if w8 is not None and ex.fp8_weight_versions != tuple(
+            w._version for w in _expert_weights(ex)):
+        return None
+    return w8
+
+
+@torch.no_grad()
+def quantize_expert(ex) -> bool:
+    """Give an Expert its weight-only fp8 copies (ops/fp8_weight.py): gate
+    and up quantised together as the packed gate|up [2F, K] weight the fused
+    kernel streams, down plain; the dequantised values are written back into
+    the three weights (exact: power-of-two row scales). False, and nothing
+    written, for a TPExpert or a shape the kernels do not take."""
+    if type(ex).__name__ != "Expert":
+        return False
+    gate, up, down = _expert_weights(ex)
+    gu8 = quantize_rows(torch.cat([gate, up]), gate_up=True)
+    d8 = quantize_rows(down)
+    if gu8 is None or d8 is None:
+        return False
+    g, u = gu8.dequant().chunk(2)
+    gate.copy_(g)
+    up.copy_(u)
+    down.copy_(d8.dequant())
+    ex.fp8_weights = (gu8, d8)
+    ex.fp8_weight_versions = tuple(w._version for w in (gate, up, down))
+    return True
+
+
 class TPExpert(nn.Module):
     """One SwiGLU expert with its weights TENSOR-sharded over the TP group
     (EP x TP composition: experts split across EP ranks, each expert's
@@ -182,12 +220,33 @@ class MoEMLP(nn.Module):
         self._ptr_tables = (key, tg, tu, td)
         return tg, tu, td
 
-    def _decode_forward(self, xt: torch.Tensor):
-        """Sync-free decode path (single process, <= 8 routed pairs):
+    def _fp8_tables(self, device):
+        """(gate|up, down) Fp8ExpertTables for the routed fp8 GEMVs, or None
+        unless every expert carries fresh fp8 weights (expert_fp8) on
+        `device`. Built lazily like _decode_tables and rebuilt when any
+        expert's Fp8Weight is no longer the one the tables point into."""
+        w8 = [expert_fp8(ex) for ex in self.experts]
+        if any(w is None or w[0].packed.device != device for w in w8):
+            self._fp8_ptr_tables = None
+            return None
+        cached = getattr(self, "_fp8_ptr_tables", None)
+        if cached is not None and all(
+                a is w[0] and b is w[1] for a, b, w in
+                zip(cached[0].experts, cached[1].experts, w8)):
+            return cached
+        self._fp8_ptr_tables = (expert_tables([w[0] for w in w8]),
+                                expert_tables([w[1] for w in w8]))
+        return self._fp8_ptr_tables
+
+    def _decode_forward(self, xt: torch.Tensor, fp8: bool = False):
+        """Sync-free decode path (single process, <= 16 routed pairs):
         router topk feeds DEVICE index tensors straight into the routed
         GEMV kernels via expert pointer tables — no bincount/argsort/
         all-to-all and no D2H slice sizes. Weight bytes scale with the
         pair count, so the grouped path stays better at prefill sizes.
+        With fp8 on and every expert quantised (quantize_expert) the two
+        GEMVs are the expert-grouped fp8 ones (ops.decode_moe_swiglu_fp8,
+        decode_moe_fp8): each hit expert streamed once, in e4m3.
         Returns None when unsupported (caller falls back)."""
         H = xt.shape[-1]
         ex = self.experts[0]
@@ -205,10 +264,19 @@ class MoEMLP(nn.Module):
         gates, idx = probs.topk(self.top_k, dim=-1)
         gates = gates / gates.sum(dim=-1, keepdim=True)
         self.aux_loss = xt.new_zeros(())        # inference: unused
-        tg, tu, td = self._decode_tables(xt.device)
         N = T * self.top_k
         idxf = idx.reshape(-1).to(torch.int64)
         xc = xt.contiguous()
+        t8 = self._fp8_tables(xt.device) if fp8 else None
+        if t8 is not None:
+            y = decode_moe_swiglu_fp8(xc, idxf, t8[0], ff, H, self.top_k)
+            z = None if y is None else decode_moe_fp8(y, idxf, t8[1], H, ff,
+                                                      1)
+            if z is not None:
+                out = (z.reshape(T, self.top_k, H).float()
+                       * gates[..., None]).sum(dim=1)
+                return out.to(xt.dtype)
+        tg, tu, td = self._decode_tables(xt.device)
         y = torch.empty(N, ff, dtype=torch.bfloat16, device=xt.device)
         rc = lib.gemv_moe_swiglu(native.stream_ptr(), tg.data_ptr(),
                                  tu.data_ptr(), idxf.data_ptr(),
@@ -224,14 +292,17 @@ class MoEMLP(nn.Module):
                * gates[..., None]).sum(dim=1)
         return out.to(xt.dtype)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
+        """fp8: serve a decode-sized step from the experts' fp8 weights
+        where they have them (the caller's weights="fp8"; the values are
+        those of the bf16 weights, so every other path is the same model)."""
         orig_shape = x.shape
         H = orig_shape[-1]
         xt = x.reshape(-1, H)
         if (not torch.is_grad_enabled() and self.tp_group is None
                 and _group_size(self.group) == 1
                 and xt.shape[0] * self.top_k <= 16):
-            fast = self._decode_forward(xt)
+            fast = self._decode_forward(xt, fp8)
             if fast is not None:
                 return fast.reshape(orig_shape)
         if self.tp_group is not None and _group_size(self.tp_group) > 1:
