@@ -23,7 +23,8 @@ from typing import List, Optional
 import torch
 
 from ..ops import (decode_linear, decode_linear_fp8, decode_swiglu,
-                   decode_swiglu_fp8, fused_rmsnorm, swiglu_packed)
+                   decode_swiglu_fp8, fp8_rows_pays, fused_rmsnorm,
+                   linear_fp8_rows, swiglu_fp8_rows, swiglu_packed)
 from ..ops.fp8_weight import quantize_rows
 from ..parallel.ep import expert_fp8, quantize_expert
 from ..parallel.tp import _group_size
@@ -121,11 +122,15 @@ def _fp8_weight(mod):
 
 def _proj(mod, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """x @ mod.weight^T through the decode GEMVs: with fp8 on, over the
-    module's fp8_weight where it has one and the kernel takes the rows,
-    else decode_linear over the (same-valued) bf16 weight."""
+    module's fp8_weight where it has one and a kernel takes the rows (the
+    GEMV up to 16; for 17..64 the skinny GEMM, where it measured faster than
+    the fallback: ops.fp8_rows_pays), else decode_linear over the
+    (same-valued) bf16 weight."""
     w8 = _fp8_weight(mod) if fp8 else None
     if w8 is not None:
         y = decode_linear_fp8(x, w8)
+        if y is None and fp8_rows_pays(x, w8):
+            y = linear_fp8_rows(x, w8)
         if y is not None:
             return y
     return decode_linear(x, mod.weight)
@@ -259,6 +264,8 @@ def _mlp_cached(mlp, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     library GEMM above 8 rows, so prefill takes the normal path)."""
     gu8 = _fp8_weight(mlp.gate_up_proj) if fp8 else None
     h = decode_swiglu_fp8(x, gu8) if gu8 is not None else None
+    if h is None and gu8 is not None and fp8_rows_pays(x, gu8):
+        h = swiglu_fp8_rows(x, gu8)
     if h is None:
         h = decode_swiglu(x, mlp.gate_up_proj.weight)
     if h is None:

@@ -638,11 +638,12 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.linear(x, weight)
 
 
-def _fp8_rows(x: torch.Tensor, w8) -> int:
-    """Rows of x if the fp8 decode GEMVs take (x, w8), else 0."""
+def _fp8_rows(x: torch.Tensor, w8, lo: int = 1, hi: int = 16) -> int:
+    """Rows of x if the fp8 decode GEMVs (lo..hi rows) take (x, w8), else
+    0."""
     K = x.shape[-1]
     rows = x.numel() // K if K else 0
-    if K != w8.K or not 1 <= rows <= 16:
+    if K != w8.K or not lo <= rows <= hi:
         return 0
     if x.is_cuda and x.dtype != torch.bfloat16:
         return 0
@@ -684,6 +685,59 @@ def decode_swiglu_fp8(x: torch.Tensor, gu8) -> Optional[torch.Tensor]:
                                 _ptr(gu8.scale), _ptr(x2), _ptr(y), F,
                                 gu8.K, rows)
     native.check_rc(rc, "gemv_fp8_swiglu", f"F={F} K={gu8.K} N={rows}")
+    return y.reshape(*x.shape[:-1], F)
+
+
+def fp8_rows_pays(x: torch.Tensor, w8) -> bool:
+    """The dispatch rule of the 17..64-row fp8 ops (hip/ops.hip
+    gemm_fp8_rows_pays): whether they measured faster over (x, w8) than the
+    bf16 weight through the library GEMM. Off the GPU there is nothing to
+    be faster than: True."""
+    if not x.is_cuda:
+        return True
+    K = x.shape[-1]
+    tiles = (w8.M // 2 if w8.gate_up else w8.M) // 16
+    return bool(_hip().gemm_fp8_rows_pays(tiles, w8.K, x.numel() // K,
+                                          int(w8.gate_up)))
+
+
+def linear_fp8_rows(x: torch.Tensor, w8) -> Optional[torch.Tensor]:
+    """decode_linear_fp8 for 17..64 rows of x (speculative verify, paged
+    prefill tails, decode above 16 slots): the fp8 skinny GEMM (hip/ops.hip
+    gemm_fp8_rows) streams the same packed weight once for all rows, and row
+    n of the result is the bits of decode_linear_fp8(x[n:n+1], w8). None
+    outside 17..64 rows and wherever decode_linear_fp8 returns None; off the
+    GPU the same reference twin runs. Inference-only."""
+    rows = _fp8_rows(x, w8, 17, 64)
+    if not rows or w8.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_linear_fp8(x, w8)
+    x2 = x.reshape(rows, w8.K).contiguous()
+    y = torch.empty(rows, w8.M, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemm_fp8_rows(native.stream_ptr(), _ptr(w8.packed),
+                              _ptr(w8.scale), _ptr(x2), _ptr(y), w8.M, w8.K,
+                              rows)
+    native.check_rc(rc, "gemm_fp8_rows", f"M={w8.M} K={w8.K} N={rows}")
+    return y.reshape(*x.shape[:-1], w8.M)
+
+
+def swiglu_fp8_rows(x: torch.Tensor, gu8) -> Optional[torch.Tensor]:
+    """decode_swiglu_fp8 for 17..64 rows (hip/ops.hip gemm_fp8_rows_swiglu):
+    [..., F], rows bit-equal to the one-row decode_swiglu_fp8; None
+    otherwise, like linear_fp8_rows."""
+    rows = _fp8_rows(x, gu8, 17, 64)
+    if not rows or not gu8.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_swiglu_fp8(x, gu8)
+    F = gu8.M // 2
+    x2 = x.reshape(rows, gu8.K).contiguous()
+    y = torch.empty(rows, F, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemm_fp8_rows_swiglu(native.stream_ptr(), _ptr(gu8.packed),
+                                     _ptr(gu8.scale), _ptr(x2), _ptr(y), F,
+                                     gu8.K, rows)
+    native.check_rc(rc, "gemm_fp8_rows_swiglu", f"F={F} K={gu8.K} N={rows}")
     return y.reshape(*x.shape[:-1], F)
 
 

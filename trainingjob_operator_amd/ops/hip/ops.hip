@@ -1746,6 +1746,190 @@ void gemv_moe_fp8_kernel(const unsigned long long* __restrict__ table_w,
 
 
 // ---------------------------------------------------------------------------
+// Weight-only fp8 skinny GEMM for 17 <= N <= 64 rows of x (speculative
+// verify, paged prefill tails, decode above 16 slots): gemv_fp8's packed
+// weight, scales and arguments, NT = ceil(N / 16) MFMA column tiles.
+//
+// One weight stream for all rows: a wave loads a 16-row A tile's k-block
+// once, converts it once (gf8_cvt8) and feeds it to NT MFMA pairs, one per
+// column tile, into NT f32x4 accumulators. Weight bytes per call are
+// gemv_fp8's whatever N is; columns n >= N of the last column tile carry
+// zeros and store nothing.
+//
+// The x traffic is the new cost: x is N * K * 2 bytes (512 KB at 64 x 4096,
+// eight times a tile's 64 KB of weight), and a wave's B fragments of one
+// k-block are NT * 2 16-byte loads against one weight load. So a wave owns R
+// ADJACENT row tiles (R * NW A tiles, contiguous in the packed layout) and
+// keeps the k-block's x fragments in registers across them: x bytes moved
+// from L2 and x load instructions per weight byte both fall by R, with no
+// LDS copy and no barrier in the k loop (the waves of a workgroup still own
+// different k, so an LDS stage would share nothing between them). A step is
+// a chunk of 8 k-blocks for one or two A tiles and half a chunk for four: 8
+// or 16 nontemporal weight loads in flight per wave, gemv_fp8's bytes.
+// R is the host's choice (gemm_fp8_rows_r): more reuse against fewer waves.
+//
+// Row n of the result is the bits of gemv_fp8 on x[n : n + 1]: the workgroup
+// is still SPLIT = gemv_fp8_split(M / 16, K) waves, wave s owns chunks s,
+// s + SPLIT, ... and walks them in ascending k, so every accumulator sees
+// gemv_fp8_kernel's MFMA sequence for its (tile, column); an MFMA column
+// depends on that column of B alone. The partial tiles then meet in LDS, one
+// row tile (pair) at a time, and are added in wave order (waves 0..NT-1 take
+// a column tile each); scale, silu(gate) * up and rounding are gemv_fp8's.
+// Reads nothing but shapes from the host; vector stores only; built without
+// packed fp32 ops (see gemv_fp8_kernel).
+// ---------------------------------------------------------------------------
+#define GF8_ROWS_MIN 17
+#define GF8_ROWS_MAX 64
+
+// four adjacent bf16 of y row n from the summed tile values: gemv_fp8's
+// epilogue, word for word
+template <bool SWIGLU>
+GEMV_NO_PK_F32 __device__ __forceinline__ void gf8_rows_store(
+    const float (&g)[4], const float (&u)[4], const float* __restrict__ scale,
+    u16* __restrict__ y, int M, int m0, int n) {
+  union { gf8_u32x2 u; u16 h[4]; } out;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float v = g[r] * scale[m0 + r];
+    if (SWIGLU) {
+      const float up = u[r] * scale[M + m0 + r];
+      v = v / (1.f + expf(-v)) * up;             // silu(gate) * up
+    }
+    out.h[r] = f2bf(v);
+  }
+  *reinterpret_cast<gf8_u32x2*>(y + (long)n * M + m0) = out.u;
+}
+
+template <int SPLIT, bool SWIGLU, int NT, int R>
+GEMV_NO_PK_F32 __global__ __launch_bounds__(64 * SPLIT)
+void gemm_fp8_rows_kernel(const gf8_u32x4* __restrict__ w8,
+                          const float* __restrict__ scale,
+                          const u16* __restrict__ x, u16* __restrict__ y,
+                          int M, int K, int N) {
+  constexpr int NW = SWIGLU ? 2 : 1;
+  constexpr int RT = R * NW;           // A tiles of 16 weight rows per wave
+  constexpr int HB = RT > 2 ? 4 : 8;   // k-blocks per step: 8 or 16 loads
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int col = lane & 15;           // column within a column tile
+  const int kg = lane >> 4;            // k group of the fragments
+  const int tile0 = blockIdx.x * R;    // first of this workgroup's row tiles
+  const int kb = K >> 6;               // k-blocks per row
+  // column tiles t < NT - 1 are full (N > 16 * (NT - 1)); only the last has
+  // dead columns, whose lanes load nothing and carry zeros
+  const bool live = (NT - 1) * 16 + col < N;
+  const gf8_u32x4* wt = w8 + (long)tile0 * NW * kb * 64 + lane;
+  // 16-byte pieces of x row (t * 16 + col) from this lane's k offset; a dead
+  // lane's pointer stays on row 0, in bounds, and is not followed
+  const gf8_u32x4* xr[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    xr[t] = reinterpret_cast<const gf8_u32x4*>(
+        x + (long)(t < NT - 1 || live ? t * 16 + col : 0) * K + kg * 16);
+  f32x4 acc[RT][NT];
+#pragma unroll
+  for (int i = 0; i < RT; ++i)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[i][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int c = wave; c < K / GF8_CHUNK; c += SPLIT) {
+#pragma unroll
+    for (int h = 0; h < 8; h += HB) {
+      gf8_u32x4 wv[RT][HB];
+#pragma unroll
+      for (int i = 0; i < RT; ++i)
+#pragma unroll
+        for (int b = 0; b < HB; ++b)
+          wv[i][b] = __builtin_nontemporal_load(
+              wt + ((long)i * kb + c * 8 + h + b) * 64);
+#pragma unroll
+      for (int b = 0; b < HB; ++b) {
+        union { gf8_u32x4 u; bf16x8 v; } xv[NT][2];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          if (t < NT - 1 || live) {
+            xv[t][0].u = xr[t][c * (GF8_CHUNK / 8) + (h + b) * 8];
+            xv[t][1].u = xr[t][c * (GF8_CHUNK / 8) + (h + b) * 8 + 1];
+          } else {
+            xv[t][0].u = xv[t][1].u = gf8_u32x4{0u, 0u, 0u, 0u};
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < RT; ++i) {
+          const bf16x8 a0 = gf8_cvt8(wv[i][b][0], wv[i][b][1]);
+          const bf16x8 a1 = gf8_cvt8(wv[i][b][2], wv[i][b][3]);
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a0, xv[t][0].v, acc[i][t], 0, 0, 0);
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a1, xv[t][1].v, acc[i][t], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // lane holds C[m0 + q][t * 16 + col], q = 0..3, of every (A tile, t)
+  if constexpr (SPLIT > 1) {
+    // one row tile (pair) per pass: partial tiles [wave][NW][NT][4][64];
+    // wave t adds column tile t in wave order and stores it
+    __shared__ float red[SPLIT * NW * NT * 4 * 64];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (r) {                         // the pass before has been read
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      }
+#pragma unroll
+      for (int j = 0; j < NW; ++j)
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            red[(((wave * NW + j) * NT + t) * 4 + q) * 64 + lane] =
+                acc[r * NW + j][t][q];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      for (int t = wave; t < NT; t += SPLIT) {
+        float s[NW][4];
+#pragma unroll
+        for (int j = 0; j < NW; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float v = red[((j * NT + t) * 4 + q) * 64 + lane];
+#pragma unroll
+            for (int w = 1; w < SPLIT; ++w)
+              v += red[(((w * NW + j) * NT + t) * 4 + q) * 64 + lane];
+            s[j][q] = v;
+          }
+        if (t < NT - 1 || live)
+          gf8_rows_store<SWIGLU>(s[0], s[NW - 1], scale, y, M,
+                                 (tile0 + r) * 16 + kg * 4, t * 16 + col);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        float s[NW][4];
+#pragma unroll
+        for (int j = 0; j < NW; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) s[j][q] = acc[r * NW + j][t][q];
+        if (t < NT - 1 || live)
+          gf8_rows_store<SWIGLU>(s[0], s[NW - 1], scale, y, M,
+                                 (tile0 + r) * 16 + kg * 4, t * 16 + col);
+      }
+  }
+}
+
+
+// ---------------------------------------------------------------------------
 // fp8 KV cache (format: ops/reference.py "fp8 KV cache", the torch twin these
 // two kernels reproduce byte for byte). Per layer a K byte pool [n_pages,
 // n_kv, 64, 128] row-major, a V byte pool of the same size holding one
@@ -2788,6 +2972,99 @@ int gemv_fp8(void* stream, const void* w8, const void* scale, const void* x,
 int gemv_fp8_swiglu(void* stream, const void* w8, const void* scale,
                     const void* x, void* y, int F, int K, int N) {
   return gemv_fp8_launch(true, stream, w8, scale, x, y, F, K, N);
+}
+
+// fp8 skinny GEMM (gemm_fp8_rows_kernel). Row tiles (gate|up: tile pairs) a
+// wave keeps its x fragments across: the largest of 4, 2, 1 (gate|up: 2, 1)
+// that divides the tiles and still leaves 1536 waves, 1.5 for each of the
+// 1024 SIMDs. Measured (profiles/r20_fp8_rows.md): llama3-8b's lm_head runs
+// 3x faster at 4 than at 1 and qkv and gate|up 1.4x to 1.6x faster at 2, but
+// o and down, left with 1024 waves at 2, are 5% to 15% slower there than at
+// 1. The split stays gemv_fp8_split of the tiles, whatever R is. Host
+// callable.
+int gemm_fp8_rows_r(int tiles, int K, int swiglu) {
+  const long split = gemv_fp8_split(tiles, K);
+  int r = swiglu ? 2 : 4;
+  while (r > 1 && (tiles % r != 0 || tiles / r * split < 1536)) r /= 2;
+  return r;
+}
+
+// Whether the skinny GEMM beats the bf16 library GEMM over the same rows
+// (1) or not (0): the dispatch rule of generate._proj, from the same
+// measurement. The kernel's time follows the x bytes its workgroups re-read
+// from L2, tiles / R * N * K * 2, and the fallback's the bf16 weight bytes;
+// their ratio is N / (16 * A) with A = R (gate|up: 2 R) A tiles per wave.
+// Every measured call at a ratio up to 1.25 won (1.13x to 2.2x), every one
+// from 2.5 lost or tied, and at 2 one won, one tied and one lost; the rule
+// is the ratio 1.5, N <= 24 A: all of 17..64 at A = 4 (lm_head, gate|up),
+// 17..48 at 2 (qkv), 17..24 at 1 (o, down). A weight under 4 MB, a launch's
+// latency on either route, is taken whatever N is.
+int gemm_fp8_rows_pays(int tiles, int K, int N, int swiglu) {
+  const int a = gemm_fp8_rows_r(tiles, K, swiglu) * (swiglu ? 2 : 1);
+  return N <= 24 * a || (long)tiles * (swiglu ? 32 : 16) * K < (4l << 20);
+}
+
+// r = 0: the rule above; 1, 2, 4: that many row tiles per wave (benchmarks)
+static int gemm_fp8_rows_launch(bool swiglu, int r, void* stream,
+                                const void* w8, const void* scale,
+                                const void* x, void* y, int M, int K, int N) {
+  if (M <= 0 || K <= 0 || (M % 16) != 0 || (K % GF8_CHUNK) != 0 ||
+      N < GF8_ROWS_MIN || N > GF8_ROWS_MAX || !w8 || !scale || !x || !y)
+    return -1;
+  const int tiles = M / 16;
+  if (r == 0) r = gemm_fp8_rows_r(tiles, K, swiglu);
+  if ((r != 1 && r != 2 && r != 4) || (swiglu && r == 4) || tiles % r != 0)
+    return -1;
+  const int nt = (N + 15) / 16;
+  dim3 grid((unsigned)(tiles / r));
+#define GF8R_LAUNCH(S, SW, NT, R) \
+  hipLaunchKernelGGL((gemm_fp8_rows_kernel<S, SW, NT, R>), grid, \
+                     dim3(64 * S), 0, STREAM, (const gf8_u32x4*)w8, \
+                     (const float*)scale, (const u16*)x, (u16*)y, M, K, N)
+#define GF8R_R(S, NT) \
+  if (swiglu) { \
+    if (r == 2) GF8R_LAUNCH(S, true, NT, 2); \
+    else GF8R_LAUNCH(S, true, NT, 1); \
+  } else { \
+    if (r == 4) GF8R_LAUNCH(S, false, NT, 4); \
+    else if (r == 2) GF8R_LAUNCH(S, false, NT, 2); \
+    else GF8R_LAUNCH(S, false, NT, 1); \
+  }
+#define GF8R_CASE(S) \
+    case S: \
+      if (nt == 2) { GF8R_R(S, 2) } \
+      else if (nt == 3) { GF8R_R(S, 3) } \
+      else { GF8R_R(S, 4) } \
+      break;
+  switch (gemv_fp8_split(tiles, K)) {
+    GF8R_CASE(1) GF8R_CASE(2) GF8R_CASE(4) GF8R_CASE(8)
+  }
+#undef GF8R_CASE
+#undef GF8R_R
+#undef GF8R_LAUNCH
+  return 0;
+}
+
+// gemv_fp8's arguments with 17 <= N <= 64 rows of x; row n of y is the bits
+// of gemv_fp8 on x row n alone.
+int gemm_fp8_rows(void* stream, const void* w8, const void* scale,
+                  const void* x, void* y, int M, int K, int N) {
+  return gemm_fp8_rows_launch(false, 0, stream, w8, scale, x, y, M, K, N);
+}
+
+// gemv_fp8_swiglu's arguments with 17 <= N <= 64
+int gemm_fp8_rows_swiglu(void* stream, const void* w8, const void* scale,
+                         const void* x, void* y, int F, int K, int N) {
+  return gemm_fp8_rows_launch(true, 0, stream, w8, scale, x, y, F, K, N);
+}
+
+// benchmark entry (scripts/gemmfp8bench.py): r row tiles per wave, forced
+int gemm_fp8_rows_ab(void* stream, int swiglu, int r, const void* w8,
+                     const void* scale, const void* x, void* y, int M, int K,
+                     int N) {
+  if (r < 1) return -1;
+  return gemm_fp8_rows_launch(swiglu != 0, r, stream, w8, scale, x, y, M, K,
+                              N);
 }
 
 // Routed fp8 decode GEMVs (gemv_moe_fp8_kernel): grid (tiles, E), the split

@@ -77,6 +77,15 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.gemv_fp8, [vp, vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_fp8_swiglu, [vp, vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_fp8_split, [i, i], i)
+    # fp8 skinny GEMM: the same arguments with 17 <= N <= 64; row tiles per
+    # wave by gemm_fp8_rows_r(tiles, K, swiglu) (host), or forced through
+    # gemm_fp8_rows_ab(stream, swiglu, r, ...) for benchmarks;
+    # gemm_fp8_rows_pays(tiles, K, N, swiglu): the measured dispatch rule
+    _sig(lib.gemm_fp8_rows, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemm_fp8_rows_swiglu, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemm_fp8_rows_r, [i, i, i], i)
+    _sig(lib.gemm_fp8_rows_pays, [i, i, i, i], i)
+    _sig(lib.gemm_fp8_rows_ab, [vp, i, i, vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_moe_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i], i)
     _sig(lib.gemv_moe, [vp, vp, vp, vp, vp, i, i, i, i], i)
     # routed fp8 GEMVs, expert-grouped: (u64 table of packed weights, u64
