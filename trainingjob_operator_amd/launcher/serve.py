@@ -7,7 +7,7 @@ families an OpenAI-ish token-in/token-out endpoint on an MI355X node:
     python -m trainingjob_operator_amd.launcher.serve \
         --model llama3-8b --port 8000 [--ckpt-dir DIR] [--graph]
         [--paged [--max-slots N] [--pool-pages N] [--prefill-chunk N]
-         [--lookup-k N] [--kv fp8]]
+         [--lookup-k N] [--kv fp8]] [--weights fp8|mxfp4]
 
 The API is deliberately token-level (``prompt_tokens`` → ``tokens``):
 tokenizers are workload assets the cluster may not have offline, and the
@@ -64,7 +64,8 @@ def create_app(model, model_name: str = "model", paged: bool = False,
     sequences over `pool_pages` 64-row KV pages (default 32 per slot);
     prefill_chunk > 0 selects the engine's paged prefill with that many
     prompt tokens per step, lookup_k > 0 its prompt-lookup speculation.
-    weights="fp8" decodes from e4m3 weights on every route; kv="fp8"
+    weights="fp8" decodes from e4m3 weights on every route and
+    weights="mxfp4" from MXFP4 weights (steps of up to 16 rows); kv="fp8"
     (paged only) keeps the KV pages in e4m3."""
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
@@ -346,10 +347,12 @@ def main(argv=None):
                     help="with --paged: prompt-lookup speculation, up to N "
                          "(<= 7) draft tokens per greedy request and step "
                          "(0 = plain decode)")
-    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16",
+    ap.add_argument("--weights", choices=("bf16", "fp8", "mxfp4"),
+                    default="bf16",
                     help="fp8: quantise the decode projections to e4m3 "
                          "(per-row power-of-two scales) and stream those in "
-                         "every step of up to 16 rows")
+                         "every step of up to 16 rows; mxfp4: to OCP MXFP4 "
+                         "(e2m1, a power-of-two scale per 32 k) instead")
     ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16",
                     help="with --paged: fp8 keeps the KV pages in e4m3 with "
                          "one scale per row and kv head (132 bytes per row "

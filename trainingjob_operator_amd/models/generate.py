@@ -22,10 +22,12 @@ from typing import List, Optional
 
 import torch
 
-from ..ops import (decode_linear, decode_linear_fp8, decode_swiglu,
-                   decode_swiglu_fp8, fp8_rows_pays, fused_rmsnorm,
-                   linear_fp8_rows, swiglu_fp8_rows, swiglu_packed)
+from ..ops import (decode_linear, decode_linear_fp8, decode_linear_mx4,
+                   decode_swiglu, decode_swiglu_fp8, decode_swiglu_mx4,
+                   fp8_rows_pays, fused_rmsnorm, linear_fp8_rows,
+                   swiglu_fp8_rows, swiglu_packed)
 from ..ops.fp8_weight import quantize_rows
+from ..ops.mx4_weight import quantize_mx4
 from ..parallel.ep import expert_fp8, quantize_expert
 from ..parallel.tp import _group_size
 from .config import LlamaConfig
@@ -51,7 +53,7 @@ def build_inference_model(cfg, device):
     return model.eval()
 
 
-def quantize_decode_weights(model) -> int:
+def quantize_decode_weights(model, fmt: str = "fp8") -> int:
     """Quantise the decode projections to weight-only fp8, once: qkv_proj,
     o_proj, gate_up_proj and down_proj of every dense block and the lm_head
     get an `fp8_weight` (ops/fp8_weight.py) next to their own weight, and
@@ -69,7 +71,17 @@ def quantize_decode_weights(model) -> int:
     remembers the version of the weight(s) it was made from: after a weight
     is written again (load_state_dict, an optimizer step) it is no longer
     used, and the next call here replaces it. Returns the number of weights
-    that now carry one; an expert counts as two (gate|up and down)."""
+    that now carry one; an expert counts as two (gate|up and down).
+
+    fmt="mxfp4" does the same for the dense projections in OCP MXFP4
+    (ops/mx4_weight.py: e2m1 values, a power-of-two scale per 32 k, written
+    back exactly too) as `mx4_weight`, for the MXFP4 GEMVs; experts are left
+    in bf16. A model carries one format: quantising to one what already
+    carries the other would requantise dequantised values and silently serve
+    a different model, so that is a ValueError."""
+    if fmt not in ("fp8", "mxfp4"):
+        raise ValueError(f"fmt must be 'fp8' or 'mxfp4', not {fmt!r}")
+    mx4 = fmt == "mxfp4"
     mods = []
     for blk in model.blocks:
         mods += [(blk.attn.qkv_proj, False), (blk.attn.o_proj, False)]
@@ -78,18 +90,33 @@ def quantize_decode_weights(model) -> int:
                      (blk.mlp.down_proj, False)]
     if model.lm_head.weight is not model.embed.weight:
         mods.append((model.lm_head, False))
+    experts = [ex for blk in model.blocks if hasattr(blk, "moe")
+               for ex in blk.moe.experts]
+    other = _fp8_weight if mx4 else _mx4_weight
+    if any(other(mod) is not None for mod, _ in mods) or (
+            mx4 and any(expert_fp8(ex) is not None for ex in experts)):
+        raise ValueError(
+            f"this model's decode weights are already quantised to "
+            f"{'fp8' if mx4 else 'mxfp4'}; {fmt!r} needs a fresh model")
     done = 0
     with torch.no_grad():
         for blk in model.blocks:
             moe = getattr(blk, "moe", None)
-            if moe is None or moe.tp_group is not None or \
+            if mx4 or moe is None or moe.tp_group is not None or \
                     _group_size(moe.group) != 1:
                 continue
             for ex in moe.experts:
                 if expert_fp8(ex) is not None or quantize_expert(ex):
                     done += 2
         for mod, gate_up in mods:
-            if _fp8_weight(mod) is None:
+            if mx4 and _mx4_weight(mod) is None:
+                w4 = quantize_mx4(mod.weight, gate_up=gate_up)
+                if w4 is None:
+                    continue
+                mod.weight.copy_(w4.dequant())
+                mod.mx4_weight = w4
+                mod.mx4_weight_version = mod.weight._version
+            elif not mx4 and _fp8_weight(mod) is None:
                 w8 = quantize_rows(mod.weight, gate_up=gate_up)
                 if w8 is None:
                     continue
@@ -102,14 +129,17 @@ def quantize_decode_weights(model) -> int:
 
 def use_fp8_weights(model, weights: str) -> bool:
     """What a `weights=` argument means for `model`: False for "bf16"; for
-    "fp8", quantise the model's decode weights if they are not yet (or are
-    stale) and return True. The caller hands the answer down to the steps
-    it runs; nothing is kept on the model but the weights themselves."""
-    if weights not in ("bf16", "fp8"):
-        raise ValueError(f"weights must be 'bf16' or 'fp8', not {weights!r}")
-    if weights == "fp8":
-        quantize_decode_weights(model)
-    return weights == "fp8"
+    "fp8" or "mxfp4", quantise the model's decode weights to that format if
+    they are not yet (or are stale) and return True: "use the modules'
+    quantised decode weights", whose type chooses the kernel. The caller
+    hands the answer down to the steps it runs; nothing is kept on the model
+    but the weights themselves."""
+    if weights not in ("bf16", "fp8", "mxfp4"):
+        raise ValueError(f"weights must be 'bf16', 'fp8' or 'mxfp4', not "
+                         f"{weights!r}")
+    if weights != "bf16":
+        quantize_decode_weights(model, weights)
+    return weights != "bf16"
 
 
 def _fp8_weight(mod):
@@ -120,17 +150,30 @@ def _fp8_weight(mod):
     return w8
 
 
+def _mx4_weight(mod):
+    """The module's Mx4Weight, unless its weight was written since."""
+    w4 = getattr(mod, "mx4_weight", None)
+    if w4 is not None and mod.mx4_weight_version != mod.weight._version:
+        return None
+    return w4
+
+
 def _proj(mod, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """x @ mod.weight^T through the decode GEMVs: with fp8 on, over the
     module's fp8_weight where it has one and a kernel takes the rows (the
     GEMV up to 16; for 17..64 the skinny GEMM, where it measured faster than
-    the fallback: ops.fp8_rows_pays), else decode_linear over the
-    (same-valued) bf16 weight."""
+    the fallback: ops.fp8_rows_pays) or over its mx4_weight (the MXFP4 GEMV,
+    up to 16 rows), else decode_linear over the (same-valued) bf16 weight."""
     w8 = _fp8_weight(mod) if fp8 else None
     if w8 is not None:
         y = decode_linear_fp8(x, w8)
         if y is None and fp8_rows_pays(x, w8):
             y = linear_fp8_rows(x, w8)
+        if y is not None:
+            return y
+    w4 = _mx4_weight(mod) if fp8 else None
+    if w4 is not None:
+        y = decode_linear_mx4(x, w4)
         if y is not None:
             return y
     return decode_linear(x, mod.weight)
@@ -266,6 +309,9 @@ def _mlp_cached(mlp, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     h = decode_swiglu_fp8(x, gu8) if gu8 is not None else None
     if h is None and gu8 is not None and fp8_rows_pays(x, gu8):
         h = swiglu_fp8_rows(x, gu8)
+    gu4 = _mx4_weight(mlp.gate_up_proj) if fp8 and h is None else None
+    if gu4 is not None:
+        h = decode_swiglu_mx4(x, gu4)
     if h is None:
         h = decode_swiglu(x, mlp.gate_up_proj.weight)
     if h is None:
@@ -367,7 +413,8 @@ def generate(model: LlamaModel, tokens: torch.Tensor,
     """Autoregressive generation: prefill the prompt once, then KV-cached
     one-token decode steps. temperature 0 = greedy. weights="fp8" streams
     the decode projections from e4m3 weights (use_fp8_weights; the model
-    is quantised in place the first time). Returns [B, prompt + generated]."""
+    is quantised in place the first time), weights="mxfp4" from OCP MXFP4
+    weights. Returns [B, prompt + generated]."""
     was_training = model.training
     model.eval()
     try:

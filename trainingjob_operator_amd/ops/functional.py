@@ -688,6 +688,44 @@ def decode_swiglu_fp8(x: torch.Tensor, gu8) -> Optional[torch.Tensor]:
     return y.reshape(*x.shape[:-1], F)
 
 
+def decode_linear_mx4(x: torch.Tensor, w4) -> Optional[torch.Tensor]:
+    """y = x @ dequant(w4)^T for 1..16 rows of bf16 x over an MXFP4 weight
+    (ops/mx4_weight.py): the matrix-core weight-only GEMV (hip/ops.hip
+    gemv_mx4), 0.27 of decode_linear's weight bytes. Returns None when it
+    does not take the call (rows, K, dtype, a gate|up weight); off the GPU
+    the reference twin runs. Inference-only."""
+    rows = _fp8_rows(x, w4)
+    if not rows or w4.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_linear_mx4(x, w4)
+    x2 = x.reshape(rows, w4.K).contiguous()
+    y = torch.empty(rows, w4.M, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemv_mx4(native.stream_ptr(), _ptr(w4.packed),
+                         _ptr(w4.scale), _ptr(x2), _ptr(y), w4.M, w4.K, rows)
+    native.check_rc(rc, "gemv_mx4", f"M={w4.M} K={w4.K} N={rows}")
+    return y.reshape(*x.shape[:-1], w4.M)
+
+
+def decode_swiglu_mx4(x: torch.Tensor, gu4) -> Optional[torch.Tensor]:
+    """silu(x @ Wg^T) * (x @ Wu^T) over a packed MXFP4 gate|up weight in one
+    kernel (hip/ops.hip gemv_mx4_swiglu): [..., F] for 1..16 rows, None
+    otherwise, like decode_linear_mx4."""
+    rows = _fp8_rows(x, gu4)
+    if not rows or not gu4.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_swiglu_mx4(x, gu4)
+    F = gu4.M // 2
+    x2 = x.reshape(rows, gu4.K).contiguous()
+    y = torch.empty(rows, F, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemv_mx4_swiglu(native.stream_ptr(), _ptr(gu4.packed),
+                                _ptr(gu4.scale), _ptr(x2), _ptr(y), F,
+                                gu4.K, rows)
+    native.check_rc(rc, "gemv_mx4_swiglu", f"F={F} K={gu4.K} N={rows}")
+    return y.reshape(*x.shape[:-1], F)
+
+
 def fp8_rows_pays(x: torch.Tensor, w8) -> bool:
     """The dispatch rule of the 17..64-row fp8 ops (hip/ops.hip
     gemm_fp8_rows_pays): whether they measured faster over (x, w8) than the

@@ -1609,6 +1609,170 @@ void gemv_fp8_kernel(const gf8_u32x4* __restrict__ w8,
 
 
 // ---------------------------------------------------------------------------
+// Weight-only MXFP4 decode GEMV on the matrix cores: y[n][M] = x[n][K] @
+// dequant(W4)[M][K]^T for n <= 16 rows (OCP MXFP4: e2m1 values, one e8m0
+// power-of-two scale per row and 32 k; bf16 x and y, fp32 accumulate). 4.25
+// bits per weight: 0.53 of gemv_fp8's bytes for the same elements.
+//
+// v_cvt_scalef32_pk_bf16_fp4 turns one byte (two e2m1, low nibble first)
+// into two bf16 with the block scale folded in - exact, e2m1 has one mantissa
+// bit - so the scale costs no VALU multiply and the epilogue has none left:
+// per 32 weights a lane issues 16 conversions and 4 v_mfma_f32_16x16x32_bf16.
+//
+// Packed weight (ops/mx4_weight.py), tile-major so that every wave-wide
+// 16-byte load is one contiguous KB:
+//   values [M/16 tiles][NW][K/128 k-blocks][64 lanes][16 bytes]
+//   scales [M/16 tiles][NW][K/512 chunks][64 lanes][4 bytes]
+// NW = 1 plain, 2 for gate|up (gate tile t and up tile t adjacent). Lane l's
+// 16 value bytes are row (l & 15), k = kblock * 128 + (l >> 4) * 32 + 0..31:
+// exactly one MX block, so ONE scale serves the load's 16 conversions, and
+// word w is the A fragment of the k-block's MFMA w. Byte i of the lane's scale
+// dword is the e8m0 byte of its block in k-block 4 * chunk + i; e8m0 -> fp32
+// is a shift into the exponent field. The B fragment uses the same k
+// permutation: 64 contiguous bytes of x row (l & 15), four 16-byte loads.
+//
+// Work split, reduction, dead columns, nontemporal loads, no host input, no
+// packed fp32 ops, no calls: gemv_fp8_kernel's contract, unchanged - SPLIT
+// waves on ONE 16-row tile, wave s owns the 512-wide chunks s, s + SPLIT, ...
+// in ascending k, partial tiles meet in LDS and wave 0 adds them in wave
+// order. A chunk is only 4 weight loads and 1 scale load per tile; with TWO
+// a wave issues the loads of its next two chunks together (8 + 2 in flight,
+// gemv_fp8's 8) and then multiplies them in k order: the MFMA sequence, and
+// so every bit of y, is the same with and without TWO. Measured
+// (profiles/r21_mxfp4_decode.md): TWO gains at most 2% on the small plain
+// shapes and loses 22% on gate|up (157 VGPRs, 3 waves per SIMD) and 5% on
+// the lm_head at 8 rows, so gemv_mx4 launches one chunk; TWO stays
+// reachable through gemv_mx4_ab. What bounds the kernel is not the weight
+// stream but the x fragments: 64 bytes of x per 16 bytes of weight and lane.
+// ---------------------------------------------------------------------------
+#define GM4_TWO false                // what gemv_mx4 launches: one chunk
+
+// 4 e2m1 bytes (one word) -> the bf16x8 A fragment of one MFMA, times scale
+__device__ __forceinline__ bf16x8 gm4_cvt8(u32 w, float scale) {
+  union { bf16x8 v; gf8_bf16x2 p[4]; } a;
+  a.p[0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
+  a.p[1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+  a.p[2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
+  a.p[3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+  return a.v;
+}
+
+template <int SPLIT, bool SWIGLU, bool TWO>
+GEMV_NO_PK_F32 __global__ __launch_bounds__(64 * SPLIT)
+void gemv_mx4_kernel(const gf8_u32x4* __restrict__ w4,
+                     const u32* __restrict__ sc4,
+                     const u16* __restrict__ x, u16* __restrict__ y,
+                     int M, int K, int N) {
+  constexpr int NW = SWIGLU ? 2 : 1;
+  constexpr int NC = TWO ? 2 : 1;      // chunks whose loads fly together
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int n = lane & 15;             // token column
+  const int kg = lane >> 4;            // k group of the fragments
+  const int tile = blockIdx.x;
+  const int kb = K >> 7;               // 128-wide k-blocks per row
+  const int nc = K / GF8_CHUNK;        // 512-wide chunks per row
+  const bool live = n < N;
+  const gf8_u32x4* wt = w4 + (long)tile * NW * kb * 64 + lane;
+  const u32* st = sc4 + (long)tile * NW * nc * 64 + lane;
+  // 16-byte pieces of x row n from this lane's k offset; dead lanes load
+  // nothing (their pointer stays on row 0, in bounds, and is not followed)
+  const gf8_u32x4* xr = reinterpret_cast<const gf8_u32x4*>(
+      x + (long)(live ? n : 0) * K + kg * 32);
+  f32x4 acc[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int c0 = wave; c0 < nc; c0 += SPLIT * NC) {
+    gf8_u32x4 wv[NC][NW][4];
+    u32 sv[NC][NW];
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+      const int c = c0 + h * SPLIT;    // wave-uniform
+      if (h == 0 || c < nc) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            wv[h][j][b] = __builtin_nontemporal_load(
+                wt + ((long)j * kb + c * 4 + b) * 64);
+          sv[h][j] = __builtin_nontemporal_load(st + ((long)j * nc + c) * 64);
+        }
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+      const int c = c0 + h * SPLIT;
+      if (h == 0 || c < nc) {
+        union { gf8_u32x4 u; bf16x8 v; } xv[4][4];
+        if (live) {
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+              xv[b][w].u = xr[c * (GF8_CHUNK / 8) + b * 16 + w];
+        } else {
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+              xv[b][w].u = gf8_u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int j = 0; j < NW; ++j) {
+            // e8m0 byte b of the dword -> 2**(byte - 127) as fp32 bits
+            const float s =
+                __builtin_bit_cast(float, ((sv[h][j] >> (8 * b)) & 255u) << 23);
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+              acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  gm4_cvt8(wv[h][j][b][w], s), xv[b][w].v, acc[j], 0, 0, 0);
+          }
+      }
+    }
+  }
+
+  if constexpr (SPLIT > 1) {
+    // partial tiles [wave][NW][4 regs][64 lanes]; wave 0 adds in wave order
+    __shared__ float red[SPLIT * NW * 4 * 64];
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        red[((wave * NW + j) * 4 + r) * 64 + lane] = acc[j][r];
+    // __syncthreads() by its builtins: the header's function would be a call
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (wave != 0) return;
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float s = red[(j * 4 + r) * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < SPLIT; ++w)
+          s += red[((w * NW + j) * 4 + r) * 64 + lane];
+        acc[j][r] = s;
+      }
+  }
+  if (!live) return;
+  // lane holds C[m0 + r][n], r = 0..3: four adjacent bf16 of y row n
+  const int m0 = tile * 16 + kg * 4;
+  union { uint2 u; u16 h[4]; } out;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float v = acc[0][r];
+    if (SWIGLU) v = v / (1.f + expf(-v)) * acc[1][r];   // silu(gate) * up
+    out.h[r] = f2bf(v);
+  }
+  *reinterpret_cast<uint2*>(y + (long)n * M + m0) = out.u;
+}
+
+
+// ---------------------------------------------------------------------------
 // Routed (MoE) fp8 decode GEMV, expert-grouped: the 16 MFMA columns are the
 // routed (token, k) pairs n < N <= 16 and the grid is (M/16 tiles, E experts).
 // Workgroup (tile, e) is SPLIT waves on one 16-row tile of expert e's packed
@@ -2972,6 +3136,64 @@ int gemv_fp8(void* stream, const void* w8, const void* scale, const void* x,
 int gemv_fp8_swiglu(void* stream, const void* w8, const void* scale,
                     const void* x, void* y, int F, int K, int N) {
   return gemv_fp8_launch(true, stream, w8, scale, x, y, F, K, N);
+}
+
+// MXFP4 decode GEMVs (gemv_mx4_kernel): waves that share one 16-row tile.
+// gemv_fp8_split's rule measured best for the half-sized tile too
+// (profiles/r21_mxfp4_decode.md), so the chunk owners are gemv_fp8's.
+int gemv_mx4_split(int tiles, int K) { return gemv_fp8_split(tiles, K); }
+
+// split 0: the rule; two: the loads of two chunks in flight per wave
+static int gemv_mx4_launch(bool swiglu, bool two, int split, void* stream,
+                           const void* w4, const void* sc4, const void* x,
+                           void* y, int M, int K, int N) {
+  if (M <= 0 || K <= 0 || (M % 16) != 0 || (K % GF8_CHUNK) != 0 || N < 1 ||
+      N > 16 || !w4 || !sc4 || !x || !y)
+    return -1;
+  const int tiles = M / 16;
+  if (split == 0) split = gemv_mx4_split(tiles, K);
+  if (split > K / GF8_CHUNK) return -1;
+  dim3 grid((unsigned)tiles);
+  switch (split) {
+#define GM4_LAUNCH(S, SW, TW) \
+    hipLaunchKernelGGL((gemv_mx4_kernel<S, SW, TW>), grid, dim3(64 * S), 0, \
+                       STREAM, (const gf8_u32x4*)w4, (const u32*)sc4, \
+                       (const u16*)x, (u16*)y, M, K, N)
+#define GM4_CASE(S) \
+    case S: \
+      if (swiglu && two) GM4_LAUNCH(S, true, true); \
+      else if (swiglu) GM4_LAUNCH(S, true, false); \
+      else if (two) GM4_LAUNCH(S, false, true); \
+      else GM4_LAUNCH(S, false, false); \
+      break;
+    GM4_CASE(1) GM4_CASE(2) GM4_CASE(4) GM4_CASE(8)
+#undef GM4_CASE
+#undef GM4_LAUNCH
+    default:
+      return -1;
+  }
+  return 0;
+}
+
+// w4, sc4: the packed [M, K] values and scale image of ops/mx4_weight.py;
+// x [N, K] and y [N, M] bf16 row-major, N <= 16, M % 16 == 0, K % 512 == 0.
+int gemv_mx4(void* stream, const void* w4, const void* sc4, const void* x,
+             void* y, int M, int K, int N) {
+  return gemv_mx4_launch(false, GM4_TWO, 0, stream, w4, sc4, x, y, M, K, N);
+}
+
+// the packed gate|up [2F, K] weight -> y [N, F]
+int gemv_mx4_swiglu(void* stream, const void* w4, const void* sc4,
+                    const void* x, void* y, int F, int K, int N) {
+  return gemv_mx4_launch(true, GM4_TWO, 0, stream, w4, sc4, x, y, F, K, N);
+}
+
+// benchmark entry (scripts/gemvmx4bench.py): chunks in flight and split forced
+int gemv_mx4_ab(void* stream, int swiglu, int two, int split, const void* w4,
+                const void* sc4, const void* x, void* y, int M, int K,
+                int N) {
+  return gemv_mx4_launch(swiglu != 0, two != 0, split, stream, w4, sc4, x, y,
+                         M, K, N);
 }
 
 // fp8 skinny GEMM (gemm_fp8_rows_kernel). Row tiles (gate|up: tile pairs) a

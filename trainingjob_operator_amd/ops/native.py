@@ -77,6 +77,14 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.gemv_fp8, [vp, vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_fp8_swiglu, [vp, vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_fp8_split, [i, i], i)
+    # MXFP4 decode GEMVs: (packed e2m1 weight, e8m0 scale image, x, y, M | F,
+    # K, N <= 16); gemv_mx4_split(tiles, K) is their split-K rule (host);
+    # gemv_mx4_ab(stream, swiglu, two, split, ...) forces the number of
+    # chunks in flight and the split, for benchmarks
+    _sig(lib.gemv_mx4, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemv_mx4_swiglu, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemv_mx4_split, [i, i], i)
+    _sig(lib.gemv_mx4_ab, [vp, i, i, i, vp, vp, vp, vp, i, i, i], i)
     # fp8 skinny GEMM: the same arguments with 17 <= N <= 64; row tiles per
     # wave by gemm_fp8_rows_r(tiles, K, swiglu) (host), or forced through
     # gemm_fp8_rows_ab(stream, swiglu, r, ...) for benchmarks;

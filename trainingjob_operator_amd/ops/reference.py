@@ -593,6 +593,20 @@ def decode_swiglu_fp8(x: torch.Tensor, gu8) -> torch.Tensor:
     return (torch.nn.functional.silu(g) * u).to(x.dtype)
 
 
+def decode_linear_mx4(x: torch.Tensor, w4) -> torch.Tensor:
+    """Twin of hip/ops.hip gemv_mx4: dequantise the MXFP4 weight (e2m1 times
+    its block's power of two), multiply in fp32, round once to x's dtype."""
+    y = x.float() @ w4.dequant().to(x.device).t()
+    return y.to(x.dtype)
+
+
+def decode_swiglu_mx4(x: torch.Tensor, gu4) -> torch.Tensor:
+    """Twin of gemv_mx4_swiglu over the packed gate|up weight [2F, K]."""
+    gu = x.float() @ gu4.dequant().to(x.device).t()
+    g, u = gu.chunk(2, dim=-1)
+    return (torch.nn.functional.silu(g) * u).to(x.dtype)
+
+
 def _moe_fp8(one, x, idx, tables, xdiv):
     rows = [one(x[n // xdiv][None], tables.experts[e])
             for n, e in enumerate(idx.tolist())]
