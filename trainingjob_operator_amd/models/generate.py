@@ -25,7 +25,8 @@ import torch
 from ..ops import (decode_linear, decode_linear_fp8, decode_linear_mx4,
                    decode_swiglu, decode_swiglu_fp8, decode_swiglu_mx4,
                    fp8_rows_pays, fused_rmsnorm, linear_fp8_rows,
-                   swiglu_fp8_rows, swiglu_packed)
+                   linear_mx4_rows, mx4_rows_pays, swiglu_fp8_rows,
+                   swiglu_mx4_rows, swiglu_packed)
 from ..ops.fp8_weight import quantize_rows
 from ..ops.mx4_weight import quantize_mx4
 from ..parallel.ep import expert_fp8, quantize_expert
@@ -162,8 +163,10 @@ def _proj(mod, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     """x @ mod.weight^T through the decode GEMVs: with fp8 on, over the
     module's fp8_weight where it has one and a kernel takes the rows (the
     GEMV up to 16; for 17..64 the skinny GEMM, where it measured faster than
-    the fallback: ops.fp8_rows_pays) or over its mx4_weight (the MXFP4 GEMV,
-    up to 16 rows), else decode_linear over the (same-valued) bf16 weight."""
+    the fallback: ops.fp8_rows_pays) or over its mx4_weight (the MXFP4 GEMV
+    up to 16 rows, the LDS-shared-x skinny GEMM for 17..64 where
+    ops.mx4_rows_pays), else decode_linear over the (same-valued) bf16
+    weight."""
     w8 = _fp8_weight(mod) if fp8 else None
     if w8 is not None:
         y = decode_linear_fp8(x, w8)
@@ -174,6 +177,8 @@ def _proj(mod, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     w4 = _mx4_weight(mod) if fp8 else None
     if w4 is not None:
         y = decode_linear_mx4(x, w4)
+        if y is None and mx4_rows_pays(x, w4):
+            y = linear_mx4_rows(x, w4)
         if y is not None:
             return y
     return decode_linear(x, mod.weight)
@@ -312,6 +317,8 @@ def _mlp_cached(mlp, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
     gu4 = _mx4_weight(mlp.gate_up_proj) if fp8 and h is None else None
     if gu4 is not None:
         h = decode_swiglu_mx4(x, gu4)
+        if h is None and mx4_rows_pays(x, gu4):
+            h = swiglu_mx4_rows(x, gu4)
     if h is None:
         h = decode_swiglu(x, mlp.gate_up_proj.weight)
     if h is None:

@@ -779,6 +779,59 @@ def swiglu_fp8_rows(x: torch.Tensor, gu8) -> Optional[torch.Tensor]:
     return y.reshape(*x.shape[:-1], F)
 
 
+def mx4_rows_pays(x: torch.Tensor, w4) -> bool:
+    """The dispatch rule of the 17..64-row MXFP4 ops (hip/ops.hip
+    gemm_mx4_rows_pays): whether they measured faster over (x, w4) than the
+    bf16 weight through the library GEMM. Off the GPU there is nothing to
+    be faster than: True."""
+    if not x.is_cuda:
+        return True
+    K = x.shape[-1]
+    tiles = (w4.M // 2 if w4.gate_up else w4.M) // 16
+    return bool(_hip().gemm_mx4_rows_pays(tiles, w4.K, x.numel() // K,
+                                          int(w4.gate_up)))
+
+
+def linear_mx4_rows(x: torch.Tensor, w4) -> Optional[torch.Tensor]:
+    """decode_linear_mx4 for 17..64 rows of x (speculative verify, paged
+    prefill tails, decode above 16 slots): the MXFP4 skinny GEMM (hip/ops.hip
+    gemm_mx4_rows) streams the same packed weight once for all rows and
+    shares x between the row tiles of a workgroup through LDS. A row's bits
+    depend neither on the row count nor on the row's place in x. None
+    outside 17..64 rows and wherever decode_linear_mx4 returns None; off the
+    GPU the same reference twin runs. Inference-only."""
+    rows = _fp8_rows(x, w4, 17, 64)
+    if not rows or w4.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_linear_mx4(x, w4)
+    x2 = x.reshape(rows, w4.K).contiguous()
+    y = torch.empty(rows, w4.M, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemm_mx4_rows(native.stream_ptr(), _ptr(w4.packed),
+                              _ptr(w4.scale), _ptr(x2), _ptr(y), w4.M, w4.K,
+                              rows)
+    native.check_rc(rc, "gemm_mx4_rows", f"M={w4.M} K={w4.K} N={rows}")
+    return y.reshape(*x.shape[:-1], w4.M)
+
+
+def swiglu_mx4_rows(x: torch.Tensor, gu4) -> Optional[torch.Tensor]:
+    """decode_swiglu_mx4 for 17..64 rows (hip/ops.hip gemm_mx4_rows_swiglu):
+    [..., F]; None otherwise, like linear_mx4_rows."""
+    rows = _fp8_rows(x, gu4, 17, 64)
+    if not rows or not gu4.gate_up:
+        return None
+    if not x.is_cuda:
+        return reference.decode_swiglu_mx4(x, gu4)
+    F = gu4.M // 2
+    x2 = x.reshape(rows, gu4.K).contiguous()
+    y = torch.empty(rows, F, dtype=torch.bfloat16, device=x.device)
+    rc = _hip().gemm_mx4_rows_swiglu(native.stream_ptr(), _ptr(gu4.packed),
+                                     _ptr(gu4.scale), _ptr(x2), _ptr(y), F,
+                                     gu4.K, rows)
+    native.check_rc(rc, "gemm_mx4_rows_swiglu", f"F={F} K={gu4.K} N={rows}")
+    return y.reshape(*x.shape[:-1], F)
+
+
 def _moe_fp8(swiglu: bool, x, idx, tables, M: int, K: int, xdiv: int):
     """The routed fp8 GEMVs' shared front: None unless everything is on the
     GPU and (x, idx, tables) is a call the kernel takes."""

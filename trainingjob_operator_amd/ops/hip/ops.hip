@@ -2094,6 +2094,243 @@ void gemm_fp8_rows_kernel(const gf8_u32x4* __restrict__ w8,
 
 
 // ---------------------------------------------------------------------------
+// Weight-only MXFP4 skinny GEMM for 17 <= N <= 64 rows of x: gemv_mx4's
+// packed values, scale image and arguments, NT = ceil(N / 16) MFMA column
+// tiles, x shared between the row tiles of a workgroup through LDS.
+//
+// What bounds gemv_mx4 and gemm_fp8_rows is the x fragments every row tile
+// re-reads from L1/L2 (64 bytes of x per 16 bytes of weight, lane and column
+// tile here), so this kernel reads x from global memory once per WORKGROUP
+// and step, not once per wave:
+//
+// Work split. A workgroup is T x S waves: wave (ti, sl) = (wave / S, wave %
+// S) owns row tile (gate|up: tile pair) blockIdx.x * T + ti - T adjacent
+// tiles, contiguous in the packed layout - and slice sl of its k. Step i of
+// the K / (128 S) steps covers the S 128-wide k-blocks i S .. i S + S - 1,
+// one contiguous k range of x; slice sl takes k-block i S + sl of it: one
+// nontemporal 16-byte weight load per A tile (exactly one MX block per
+// lane, one scale), converted once by gm4_cvt8 (scale folded in, nothing
+// left for the epilogue) and used for NT MFMAs per word. The weight never
+// touches LDS; its loads run two steps ahead of their use. A wave whose
+// tile lies past the last one (T does not divide the tiles) stages x and
+// keeps the barriers, and loads, multiplies and stores nothing.
+//
+// x through LDS. The step's x block, rows n < N by S * 128 k, is loaded by
+// all 64 T S threads with coalesced 16-byte global loads (thread u takes
+// 16-byte unit u, u + 64 T S, ... of the row-major block) into registers one
+// step ahead, under the step's conversions and MFMAs, and written to the
+// stage buffer the NEXT step reads; two buffers, so loads never land in the
+// array being read and one barrier per step orders both (a buffer is
+// rewritten only after the barrier that ends the step that read it). Global
+// x bytes per call are tiles / T * N * K * 2: T times fewer than the
+// one-tile-per-workgroup grid, and T = 1 (no sharing, same stage) is
+// reachable through gemm_mx4_rows_ab to measure that against.
+//
+// Stage layout: [row n][S * 16 + 1 units of 16 bytes], unit c < S * 16 of a
+// row being k = step k0 + 8 c .. 8 c + 7; the last unit is padding. The B
+// fragment of lane (col, kg) for column tile t and MFMA w is unit
+// (t * 16 + col) * (16 S + 1) + sl * 16 + kg * 4 + w: four 16-byte LDS reads
+// of 64 contiguous bytes. A row stride of 1 mod 16 units puts the 16 lanes
+// of one kg (same w, rows col = 0..15) on 16 different 16-byte bank groups:
+// unit mod 16 = (col + 4 kg + w) mod 16. A 16-byte read is served a quarter
+// wave at a time (16 lanes x 16 bytes = the 64 banks x 4 bytes of a gfx950
+// LDS), and on the 32-bank model 8 lanes at a time, which the same stride
+// keeps distinct: conflict-free in both, where the unpadded [row][k] image
+// would put all 16 rows of a read on one bank group (16 ways). The writes
+// are row-major runs of 16 consecutive units per 16 lanes, row-aligned:
+// conflict-free too. Dead columns of the last column tile stage nothing,
+// read nothing (zeros) and store nothing.
+//
+// LDS is two stage buffers, NT * 16 * (16 S + 1) * 16 bytes each (16.3 KB per
+// column tile and slice: 17 to 133 KB); the S-way reduction reuses them
+// after the last step's barrier. Partial tiles of slices 1 .. S-1 meet
+// there and the tile's slice-0 wave adds them in slice order: no atomics,
+// nothing crosses workgroups, and (T, S) is a host rule of the weight alone
+// (gemm_mx4_rows_shape), so a row's bits depend neither on N nor on where
+// the row sits in x. Not bit-equal to gemv_mx4, whose waves own other k.
+// SwiGLU is silu(gate) * up on the raw sums. Reads nothing but shapes from
+// the host; vector stores only; no packed fp32 ops; barriers by builtins.
+// ---------------------------------------------------------------------------
+#define GM4R_ROWS_MIN 17
+#define GM4R_ROWS_MAX 64
+
+template <int NT, bool SWIGLU, int T, int S>
+GEMV_NO_PK_F32 __global__ __launch_bounds__(64 * T * S)
+void gemm_mx4_rows_kernel(const gf8_u32x4* __restrict__ w4,
+                          const u32* __restrict__ sc4,
+                          const u16* __restrict__ x, u16* __restrict__ y,
+                          int M, int K, int N) {
+  constexpr int NW = SWIGLU ? 2 : 1;
+  constexpr int NTH = 64 * T * S;
+  constexpr int ROWU = S * 16;         // 16-byte units of a staged row
+  constexpr int STRIDE = ROWU + 1;     // padded: 1 mod 16 units
+  constexpr int UNITS = NT * 16 * ROWU;
+  constexpr int UPT = (UNITS + NTH - 1) / NTH;   // units per thread and step
+  constexpr int BUF = NT * 16 * STRIDE;
+  static_assert(T * (S - 1) * NW * NT * 256 * 4 <= 2 * BUF * 16,
+                "the reduction reuses the stage buffers");
+  __shared__ gf8_u32x4 stage[2 * BUF];
+
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int col = lane & 15;           // column within a column tile
+  const int kg = lane >> 4;            // k group of the fragments
+  const int ti = wave / S, sl = wave % S;
+  const int tile = blockIdx.x * T + ti;
+  const bool has = tile < M / 16;      // wave-uniform: a tile to work on
+  const int kb = K >> 7;               // 128-wide k-blocks per row
+  const int nc = K / GF8_CHUNK;        // 512-wide chunks (scale dwords)
+  const int steps = kb / S;            // kb % 4 == 0 and S is 1, 2 or 4
+  const bool live = (NT - 1) * 16 + col < N;
+  const gf8_u32x4* wt = w4 + (long)(has ? tile : 0) * NW * kb * 64 + lane;
+  const u32* st = sc4 + (long)(has ? tile : 0) * NW * nc * 64 + lane;
+  // the units this thread stages: row and offset within the staged row
+  int srow[UPT], scu[UPT];
+#pragma unroll
+  for (int j = 0; j < UPT; ++j) {
+    const int u = tid + j * NTH;
+    srow[j] = u < UNITS ? u / ROWU : N;            // N: nothing to stage
+    scu[j] = u % ROWU;
+  }
+
+  f32x4 acc[NW][NT];
+#pragma unroll
+  for (int j = 0; j < NW; ++j)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  gf8_u32x4 xg[UPT];                   // the next step's x, on its way
+  gf8_u32x4 wa[NW], wb[NW], wc[NW];    // weights of steps i, i + 1, i + 2
+  u32 sa[NW], sb[NW], sc[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {       // rotated below before they are loaded
+    wa[j] = wb[j] = wc[j] = gf8_u32x4{0u, 0u, 0u, 0u};
+    sa[j] = sb[j] = sc[j] = 0u;
+  }
+#define GM4R_XLOAD(I) \
+  _Pragma("unroll") for (int j = 0; j < UPT; ++j) \
+    if (srow[j] < N) \
+      xg[j] = *reinterpret_cast<const gf8_u32x4*>( \
+          x + (long)srow[j] * K + (long)(I) * (S * 128) + scu[j] * 8)
+#define GM4R_XSTORE(B) \
+  _Pragma("unroll") for (int j = 0; j < UPT; ++j) \
+    if (srow[j] < N) stage[(B) * BUF + srow[j] * STRIDE + scu[j]] = xg[j]
+#define GM4R_WLOAD(W, SC, I) \
+  _Pragma("unroll") for (int j = 0; j < NW; ++j) { \
+    const int b = (I) * S + sl; \
+    W[j] = __builtin_nontemporal_load(wt + ((long)j * kb + b) * 64); \
+    SC[j] = st[((long)j * nc + (b >> 2)) * 64]; \
+  }
+#define GM4R_BARRIER() \
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
+  __builtin_amdgcn_s_barrier(); \
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup")
+
+  GM4R_XLOAD(0);
+  if (has) {
+    GM4R_WLOAD(wa, sa, 0);
+    if (steps > 1) { GM4R_WLOAD(wb, sb, 1); }
+  }
+  GM4R_XSTORE(0);
+  GM4R_BARRIER();
+
+  for (int i = 0; i < steps; ++i) {
+    const int buf = i & 1;
+    if (i + 1 < steps) { GM4R_XLOAD(i + 1); }
+    if (has) {
+      if (i + 2 < steps) { GM4R_WLOAD(wc, sc, i + 2); }
+      union { gf8_u32x4 u; bf16x8 v; } xv[NT][4];
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          if (t < NT - 1 || live)
+            xv[t][w].u = stage[buf * BUF + (t * 16 + col) * STRIDE + sl * 16 +
+                               kg * 4 + w];
+          else
+            xv[t][w].u = gf8_u32x4{0u, 0u, 0u, 0u};
+        }
+      const int byte = (i * S + sl) & 3;           // of the chunk's scale dword
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        // e8m0 byte -> 2**(byte - 127) as fp32 bits
+        const float s =
+            __builtin_bit_cast(float, ((sa[j] >> (8 * byte)) & 255u) << 23);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const bf16x8 a = gm4_cvt8(wa[j][w], s);
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                a, xv[t][w].v, acc[j][t], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        wa[j] = wb[j]; sa[j] = sb[j];
+        wb[j] = wc[j]; sb[j] = sc[j];
+      }
+    }
+    if (i + 1 < steps) { GM4R_XSTORE(buf ^ 1); }
+    GM4R_BARRIER();                    // step i read, step i + 1 staged
+  }
+
+  // lane holds C[m0 + q][t * 16 + col], q = 0..3, of every (A tile, t)
+  if constexpr (S > 1) {
+    // partial tiles [ti][slice - 1][NW][NT][4][64] over the stage buffers,
+    // which every wave has left (the loop ends on a barrier)
+    float* red = reinterpret_cast<float*>(stage);
+    if (has && sl > 0) {
+#pragma unroll
+      for (int j = 0; j < NW; ++j)
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            red[((((ti * (S - 1) + sl - 1) * NW + j) * NT + t) * 4 + q) * 64 +
+                lane] = acc[j][t][q];
+    }
+    GM4R_BARRIER();
+    if (sl > 0) return;
+    if (has) {
+#pragma unroll
+      for (int p = 0; p < S - 1; ++p)  // slice order
+#pragma unroll
+        for (int j = 0; j < NW; ++j)
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              acc[j][t][q] +=
+                  red[((((ti * (S - 1) + p) * NW + j) * NT + t) * 4 + q) * 64 +
+                      lane];
+    }
+  }
+#undef GM4R_BARRIER
+#undef GM4R_WLOAD
+#undef GM4R_XSTORE
+#undef GM4R_XLOAD
+  if (!has) return;
+  // four adjacent bf16 of y row t * 16 + col: gemv_mx4's epilogue
+  const int m0 = tile * 16 + kg * 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t < NT - 1 || live) {
+      union { gf8_u32x2 u; u16 h[4]; } out;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float v = acc[0][t][q];
+        if (SWIGLU) v = v / (1.f + expf(-v)) * acc[NW - 1][t][q];
+        out.h[q] = f2bf(v);
+      }
+      *reinterpret_cast<gf8_u32x2*>(y + (long)(t * 16 + col) * M + m0) = out.u;
+    }
+  }
+}
+
+
+// ---------------------------------------------------------------------------
 // fp8 KV cache (format: ops/reference.py "fp8 KV cache", the torch twin these
 // two kernels reproduce byte for byte). Per layer a K byte pool [n_pages,
 // n_kv, 64, 128] row-major, a V byte pool of the same size holding one
@@ -3286,6 +3523,105 @@ int gemm_fp8_rows_ab(void* stream, int swiglu, int r, const void* w8,
                      int N) {
   if (r < 1) return -1;
   return gemm_fp8_rows_launch(swiglu != 0, r, stream, w8, scale, x, y, M, K,
+                              N);
+}
+
+// MXFP4 skinny GEMM (gemm_mx4_rows_kernel): the workgroup is T row tiles
+// (gate|up: tile pairs) sharing one staged x by S k slices; returned as
+// T << 8 | S. Measured on llama3-8b's shapes (profiles/r22_mx4_rows.md): 8
+// waves per workgroup won everywhere, and T is the largest of 4, 2, 1 that
+// leaves 192 workgroups - (4, 2) for gate|up and the lm_head, 1.7x to 3.3x
+// faster than T = 1 at the same S; (2, 4) for qkv's 384 tiles; (1, 4) for
+// the 256 tiles of o and down, where sharing would idle CUs. A rule of the
+// weight alone, never of N, so a row's bits do not depend on the rows it is
+// batched with. Host callable.
+int gemm_mx4_rows_shape(int tiles, int K, int swiglu) {
+  (void)K;
+  (void)swiglu;
+  int t = 4;
+  while (t > 1 && tiles / t < 192) t /= 2;
+  return t << 8 | (t == 4 ? 2 : 4);
+}
+
+// Whether the kernel beats the bf16 library GEMM over the same rows (1) or
+// not (0): the dispatch rule of generate._proj, from the same tables, by
+// the T of the shape rule. T = 4 (gate|up, lm_head) won at every N, 1.17x
+// to 2.6x. T = 2 (qkv) won at 17, 32 and 40 rows and lost at 64, so rows
+// above 40 go to the losing side. T = 1 won only o at 17 rows (11.5 us
+// against 13.1) and lost from 32 and on every row count of down (K =
+// 14336): 17 rows at K <= 4096. A weight under 4 MB in bf16 is a launch's
+// latency on either route and is taken whatever N is.
+int gemm_mx4_rows_pays(int tiles, int K, int N, int swiglu) {
+  if ((long)tiles * (swiglu ? 32 : 16) * K * 2 < (4l << 20)) return 1;
+  const int t = gemm_mx4_rows_shape(tiles, K, swiglu) >> 8;
+  if (t == 4) return 1;
+  if (t == 2) return N <= 40;
+  return N <= 17 && K <= 4096;
+}
+
+// t = s = 0: the rule above; else T and S in 1, 2, 4 with T S <= 8, forced
+static int gemm_mx4_rows_launch(bool swiglu, int t, int s, void* stream,
+                                const void* w4, const void* sc4,
+                                const void* x, void* y, int M, int K, int N) {
+  if (M <= 0 || K <= 0 || (M % 16) != 0 || (K % GF8_CHUNK) != 0 ||
+      N < GM4R_ROWS_MIN || N > GM4R_ROWS_MAX || !w4 || !sc4 || !x || !y)
+    return -1;
+  const int tiles = M / 16;
+  if (t == 0 && s == 0) {
+    const int ts = gemm_mx4_rows_shape(tiles, K, swiglu);
+    t = ts >> 8;
+    s = ts & 255;
+  }
+  // 16 waves would leave each 128 VGPRs, which the k loop spills from
+  if ((t != 1 && t != 2 && t != 4) || (s != 1 && s != 2 && s != 4) ||
+      t * s > 8)
+    return -1;
+  const int nt = (N + 15) / 16;
+  dim3 grid((unsigned)((tiles + t - 1) / t));
+#define GM4R_LAUNCH(NT, SW, T, S) \
+  hipLaunchKernelGGL((gemm_mx4_rows_kernel<NT, SW, T, S>), grid, \
+                     dim3(64 * T * S), 0, STREAM, (const gf8_u32x4*)w4, \
+                     (const u32*)sc4, (const u16*)x, (u16*)y, M, K, N)
+#define GM4R_S(NT, SW, T) \
+  if (s == 1) GM4R_LAUNCH(NT, SW, T, 1); \
+  else if (s == 2) GM4R_LAUNCH(NT, SW, T, 2); \
+  else GM4R_LAUNCH(NT, SW, T, 4);
+#define GM4R_T(NT, SW) \
+  if (t == 1) { GM4R_S(NT, SW, 1) } \
+  else if (t == 2) { GM4R_S(NT, SW, 2) } \
+  else if (s == 1) GM4R_LAUNCH(NT, SW, 4, 1); \
+  else GM4R_LAUNCH(NT, SW, 4, 2);
+#define GM4R_NT(SW) \
+  if (nt == 2) { GM4R_T(2, SW) } \
+  else if (nt == 3) { GM4R_T(3, SW) } \
+  else { GM4R_T(4, SW) }
+  if (swiglu) { GM4R_NT(true) } else { GM4R_NT(false) }
+#undef GM4R_NT
+#undef GM4R_T
+#undef GM4R_S
+#undef GM4R_LAUNCH
+  return 0;
+}
+
+// gemv_mx4's arguments with 17 <= N <= 64 rows of x
+int gemm_mx4_rows(void* stream, const void* w4, const void* sc4,
+                  const void* x, void* y, int M, int K, int N) {
+  return gemm_mx4_rows_launch(false, 0, 0, stream, w4, sc4, x, y, M, K, N);
+}
+
+// gemv_mx4_swiglu's arguments with 17 <= N <= 64
+int gemm_mx4_rows_swiglu(void* stream, const void* w4, const void* sc4,
+                         const void* x, void* y, int F, int K, int N) {
+  return gemm_mx4_rows_launch(true, 0, 0, stream, w4, sc4, x, y, F, K, N);
+}
+
+// benchmark and test entry (scripts/gemmmx4bench.py): (T, S) forced; T = 1
+// is the grid that shares x between no tiles
+int gemm_mx4_rows_ab(void* stream, int swiglu, int t, int s, const void* w4,
+                     const void* sc4, const void* x, void* y, int M, int K,
+                     int N) {
+  if (t < 1 || s < 1) return -1;
+  return gemm_mx4_rows_launch(swiglu != 0, t, s, stream, w4, sc4, x, y, M, K,
                               N);
 }
 

@@ -94,6 +94,16 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     _sig(lib.gemm_fp8_rows_r, [i, i, i], i)
     _sig(lib.gemm_fp8_rows_pays, [i, i, i, i], i)
     _sig(lib.gemm_fp8_rows_ab, [vp, i, i, vp, vp, vp, vp, i, i, i], i)
+    # MXFP4 skinny GEMM: gemv_mx4's arguments with 17 <= N <= 64;
+    # gemm_mx4_rows_shape(tiles, K, swiglu) -> T << 8 | S, the row tiles that
+    # share one staged x and the k slices of a workgroup (host), or forced
+    # through gemm_mx4_rows_ab(stream, swiglu, t, s, ...) with t s <= 8;
+    # gemm_mx4_rows_pays(tiles, K, N, swiglu): the measured dispatch rule
+    _sig(lib.gemm_mx4_rows, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemm_mx4_rows_swiglu, [vp, vp, vp, vp, vp, i, i, i], i)
+    _sig(lib.gemm_mx4_rows_shape, [i, i, i], i)
+    _sig(lib.gemm_mx4_rows_pays, [i, i, i, i], i)
+    _sig(lib.gemm_mx4_rows_ab, [vp, i, i, i, vp, vp, vp, vp, i, i, i], i)
     _sig(lib.gemv_moe_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i], i)
     _sig(lib.gemv_moe, [vp, vp, vp, vp, vp, i, i, i, i], i)
     # routed fp8 GEMVs, expert-grouped: (u64 table of packed weights, u64
