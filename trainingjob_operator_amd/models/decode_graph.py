@@ -151,7 +151,8 @@ class DecodeSession:
 
     weights="fp8" captures the step over the model's e4m3 decode weights
     (generate.use_fp8_weights): half the bytes per token, same model;
-    weights="mxfp4" over its MXFP4 ones, 0.27 of the bytes.
+    weights="mxfp4" over its MXFP4 ones, 0.27 of the bytes. Both include
+    the experts of an unsharded MoE model (routed, expert-grouped GEMVs).
     """
 
     def __init__(self, model, batch: int, max_len: int,

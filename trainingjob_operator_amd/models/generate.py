@@ -29,7 +29,8 @@ from ..ops import (decode_linear, decode_linear_fp8, decode_linear_mx4,
                    swiglu_mx4_rows, swiglu_packed)
 from ..ops.fp8_weight import quantize_rows
 from ..ops.mx4_weight import quantize_mx4
-from ..parallel.ep import expert_fp8, quantize_expert
+from ..parallel.ep import (expert_fp8, expert_mx4, quantize_expert,
+                           quantize_expert_mx4)
 from ..parallel.tp import _group_size
 from .config import LlamaConfig
 from .llama import LlamaModel, _sdpa
@@ -74,10 +75,12 @@ def quantize_decode_weights(model, fmt: str = "fp8") -> int:
     used, and the next call here replaces it. Returns the number of weights
     that now carry one; an expert counts as two (gate|up and down).
 
-    fmt="mxfp4" does the same for the dense projections in OCP MXFP4
-    (ops/mx4_weight.py: e2m1 values, a power-of-two scale per 32 k, written
-    back exactly too) as `mx4_weight`, for the MXFP4 GEMVs; experts are left
-    in bf16. A model carries one format: quantising to one what already
+    fmt="mxfp4" does the same in OCP MXFP4 (ops/mx4_weight.py: e2m1 values,
+    a power-of-two scale per 32 k, written back exactly too): the dense
+    projections get an `mx4_weight` for the MXFP4 GEMVs, and the experts of
+    an unsharded MoE block their (gate|up, down) pair (parallel/ep.py
+    quantize_expert_mx4) for the routed MXFP4 GEMVs, counted the same way.
+    A model carries one format: quantising to one what already
     carries the other would requantise dequantised values and silently serve
     a different model, so that is a ValueError."""
     if fmt not in ("fp8", "mxfp4"):
@@ -94,8 +97,9 @@ def quantize_decode_weights(model, fmt: str = "fp8") -> int:
     experts = [ex for blk in model.blocks if hasattr(blk, "moe")
                for ex in blk.moe.experts]
     other = _fp8_weight if mx4 else _mx4_weight
-    if any(other(mod) is not None for mod, _ in mods) or (
-            mx4 and any(expert_fp8(ex) is not None for ex in experts)):
+    other_ex = expert_fp8 if mx4 else expert_mx4
+    if any(other(mod) is not None for mod, _ in mods) or any(
+            other_ex(ex) is not None for ex in experts):
         raise ValueError(
             f"this model's decode weights are already quantised to "
             f"{'fp8' if mx4 else 'mxfp4'}; {fmt!r} needs a fresh model")
@@ -103,11 +107,13 @@ def quantize_decode_weights(model, fmt: str = "fp8") -> int:
     with torch.no_grad():
         for blk in model.blocks:
             moe = getattr(blk, "moe", None)
-            if mx4 or moe is None or moe.tp_group is not None or \
+            if moe is None or moe.tp_group is not None or \
                     _group_size(moe.group) != 1:
                 continue
+            has, make = (expert_mx4, quantize_expert_mx4) if mx4 else \
+                (expert_fp8, quantize_expert)
             for ex in moe.experts:
-                if expert_fp8(ex) is not None or quantize_expert(ex):
+                if has(ex) is not None or make(ex):
                     done += 2
         for mod, gate_up in mods:
             if mx4 and _mx4_weight(mod) is None:

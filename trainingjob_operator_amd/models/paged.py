@@ -488,7 +488,9 @@ class PagedEngine:
     rows from e4m3 weights (generate.use_fp8_weights; the model is
     quantised in place the first time, and computes the same logits either
     way up to summation order); weights="mxfp4" does the same with OCP
-    MXFP4 weights (a model carries one of the two formats).
+    MXFP4 weights (a model carries one of the two formats). Either way the
+    experts of an unsharded MoE model are quantised too and steps of up to
+    16 routed pairs run the expert-grouped routed GEMVs.
 
     kv="fp8" keeps the pages in e4m3 (PagedKVCache(kv_dtype="fp8")): half
     the bytes per cached row, so twice the rows in the same pool bytes (the

@@ -11,6 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import native, reference
+from .mx4_weight import Mx4ExpertTables
 
 
 def _hip():
@@ -832,9 +833,11 @@ def swiglu_mx4_rows(x: torch.Tensor, gu4) -> Optional[torch.Tensor]:
     return y.reshape(*x.shape[:-1], F)
 
 
-def _moe_fp8(swiglu: bool, x, idx, tables, M: int, K: int, xdiv: int):
-    """The routed fp8 GEMVs' shared front: None unless everything is on the
-    GPU and (x, idx, tables) is a call the kernel takes."""
+def _moe_fp8(swiglu: bool, x, idx, tables, M: int, K: int, xdiv: int,
+             fmt: str = "fp8"):
+    """The routed fp8 (fmt "mx4": MXFP4) GEMVs' shared front: None unless
+    everything is on the GPU and (x, idx, tables) is a call the kernel
+    takes."""
     N = idx.numel()
     rows_w = 2 * M if swiglu else M
     if not (x.is_cuda and idx.is_cuda and x.dtype == torch.bfloat16
@@ -848,11 +851,11 @@ def _moe_fp8(swiglu: bool, x, idx, tables, M: int, K: int, xdiv: int):
     xc, ic = x.contiguous(), idx.contiguous()
     y = torch.empty(N, M, dtype=torch.bfloat16, device=x.device)
     lib = _hip()
-    fn = lib.gemv_moe_fp8_swiglu if swiglu else lib.gemv_moe_fp8
-    rc = fn(native.stream_ptr(), _ptr(tables.w), _ptr(tables.s), _ptr(ic),
-            _ptr(xc), _ptr(y), M, K, N, len(tables.experts), xdiv)
-    native.check_rc(rc, "gemv_moe_fp8_swiglu" if swiglu else "gemv_moe_fp8",
-                    f"M={M} K={K} N={N} xdiv={xdiv}")
+    name = f"gemv_moe_{fmt}_swiglu" if swiglu else f"gemv_moe_{fmt}"
+    rc = getattr(lib, name)(
+        native.stream_ptr(), _ptr(tables.w), _ptr(tables.s), _ptr(ic),
+        _ptr(xc), _ptr(y), M, K, N, len(tables.experts), xdiv)
+    native.check_rc(rc, name, f"M={M} K={K} N={N} xdiv={xdiv}")
     return y
 
 
@@ -875,6 +878,29 @@ def decode_moe_swiglu_fp8(x: torch.Tensor, idx: torch.Tensor, tables, F: int,
     """decode_moe_fp8 over the experts' packed gate|up [2F, K] weights with
     silu(gate) * up in the epilogue (gemv_moe_fp8_swiglu): [N, F] bf16."""
     return _moe_fp8(True, x, idx, tables, F, K, xdiv)
+
+
+def decode_moe_mx4(x: torch.Tensor, idx: torch.Tensor, tables, M: int,
+                   K: int, xdiv: int) -> Optional[torch.Tensor]:
+    """decode_moe_fp8 over MXFP4 experts (hip/ops.hip gemv_moe_mx4): tables
+    is the Mx4ExpertTables (ops/mx4_weight.py) of the experts' plain [M, K]
+    weights; a hit expert is streamed once at 4.25 bits per weight. Pair n's
+    row is the bits of decode_linear_mx4(x[n // xdiv][None], expert idx[n]).
+    Same contract otherwise: idx stays on the device, an index outside
+    [0, E) leaves its row of y unwritten, None off the GPU or for a call the
+    kernel does not take (tables of another format among them)."""
+    if not isinstance(tables, Mx4ExpertTables):
+        return None
+    return _moe_fp8(False, x, idx, tables, M, K, xdiv, "mx4")
+
+
+def decode_moe_swiglu_mx4(x: torch.Tensor, idx: torch.Tensor, tables, F: int,
+                          K: int, xdiv: int) -> Optional[torch.Tensor]:
+    """decode_moe_mx4 over the experts' packed gate|up [2F, K] weights with
+    silu(gate) * up in the epilogue (gemv_moe_mx4_swiglu): [N, F] bf16."""
+    if not isinstance(tables, Mx4ExpertTables):
+        return None
+    return _moe_fp8(True, x, idx, tables, F, K, xdiv, "mx4")
 
 
 # ---------------------------------------------------------------------------

@@ -1910,6 +1910,179 @@ void gemv_moe_fp8_kernel(const unsigned long long* __restrict__ table_w,
 
 
 // ---------------------------------------------------------------------------
+// Routed (MoE) MXFP4 decode GEMV, expert-grouped: gemv_moe_fp8_kernel's work
+// split over gemv_mx4_kernel's data path. Grid (M/16 tiles, E experts);
+// workgroup (tile, e) is SPLIT waves on one 16-row tile of expert e; the 16
+// MFMA columns are the routed pairs n < N <= 16 and column n is live iff
+// idx[n] == e. Bytes streamed per call: (distinct experts hit) x (expert
+// bytes at 4.25 bits), 0.27 of one bf16 expert per hit expert where the bf16
+// routed kernels stream a whole bf16 expert per PAIR.
+//
+//   gemv_moe_mx4_swiglu: y[n] = silu(Wg[e_n] @ x[n / xdiv]) * (Wu[e_n] @ ..)
+//   gemv_moe_mx4:        y[n] = W[e_n] @ x[n / xdiv]
+//
+// table_w / table_s are device u64 arrays, one entry per expert, of the
+// packed e2m1 values and of the e8m0 scale image (ops/mx4_weight.py; the
+// layout above gemv_mx4_kernel). An index is only ever COMPARED with the
+// workgroup's own expert id, never added to a pointer: a pair whose index
+// lies outside [0, E) is live nowhere and its output row is left unwritten.
+// A workgroup with no live column (the ballot is the same in all its waves:
+// liveness depends on lane & 15 alone) returns before it reads either table
+// and before any barrier.
+//
+// Per 128-wide k-block a lane issues one nontemporal 16-byte weight load
+// through the table entry (cast to address_space(1): global_load, not flat),
+// per 512-wide chunk one scale dword; gm4_cvt8 folds the block scale into
+// the conversion, four v_mfma_f32_16x16x32_bf16 per k-block and tile. The B
+// operand is 64 contiguous bytes of x row n / xdiv; dead columns carry zeros
+// and load nothing. Chunk c belongs to wave c % SPLIT with SPLIT =
+// gemv_mx4_split(M / 16, K) of ONE expert, walked in ascending k; partial
+// tiles meet in LDS, wave 0 adds them in wave order, applies silu(gate) * up
+// and stores 8 bytes per live lane. That is gemv_mx4_kernel's MFMA sequence
+// for the (tile, column), and an MFMA column depends on that column of B
+// alone: pair n's row is the bits of a one-row gemv_mx4 over its expert,
+// whatever the other pairs are routed to.
+//
+// What differs from the dense kernel is what bounds it. At MoE decode few
+// columns are live per expert (one pair per hit expert at batch 1), so the x
+// fragments are a few KB that stay in L2 and the call is bound by the latency
+// of the weight stream: a chunk is only 4 weight loads and 1 scale load per
+// tile in flight, half of the fp8 kernel's bytes. With TWO a wave issues the
+// loads of its next two chunks together (8 + 2 per tile) and multiplies them
+// in k order: the MFMA sequence and every bit of y are the same. Measured
+// at 1, 2, 4 and 8 hit experts of moe-8x7b (profiles/r23_moe_mxfp4.md): TWO
+// is 26-28% slower on gate|up everywhere (157 VGPRs, 3 waves per SIMD
+// instead of 4: what hides this latency is resident waves, not loads per
+// wave) and within +-3% on down, so the entries launch one chunk (GMM4_TWO)
+// and TWO stays reachable through gemv_moe_mx4_ab. No host input but
+// shapes, vector stores only, no calls (builtins and ext-vector types).
+// ---------------------------------------------------------------------------
+typedef __attribute__((address_space(1))) u32 gm4_global_u32;
+
+template <int SPLIT, bool SWIGLU, bool TWO>
+GEMV_NO_PK_F32 __global__ __launch_bounds__(64 * SPLIT)
+void gemv_moe_mx4_kernel(const unsigned long long* __restrict__ table_w,
+                         const unsigned long long* __restrict__ table_s,
+                         const long* __restrict__ idx,
+                         const u16* __restrict__ x, u16* __restrict__ y,
+                         int M, int K, int N, int xdiv) {
+  constexpr int NW = SWIGLU ? 2 : 1;
+  constexpr int NC = TWO ? 2 : 1;      // chunks whose loads fly together
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int n = lane & 15;             // routed pair column
+  const int kg = lane >> 4;            // k group of the fragments
+  const int tile = blockIdx.x;
+  const int e = blockIdx.y;
+  const int kb = K >> 7;               // 128-wide k-blocks per row
+  const int nc = K / GF8_CHUNK;        // 512-wide chunks per row
+  const bool live = n < N && idx[n < N ? n : 0] == (long)e;
+  if (__builtin_amdgcn_ballot_w64(live) == 0) return;   // expert not hit
+
+  // table entries are device (global) addresses: say so, or the loads
+  // through them become flat loads
+  const gf8_global_u32x4* wt = (const gf8_global_u32x4*)table_w[e] +
+                               (long)tile * NW * kb * 64 + lane;
+  const gm4_global_u32* st = (const gm4_global_u32*)table_s[e] +
+                             (long)tile * NW * nc * 64 + lane;
+  // 16-byte pieces of pair n's x row from this lane's k offset; dead lanes
+  // load nothing (their pointer stays on row 0 and is not followed)
+  const gf8_u32x4* xr = reinterpret_cast<const gf8_u32x4*>(
+      x + (long)(live ? n / xdiv : 0) * K + kg * 32);
+  f32x4 acc[NW];
+#pragma unroll
+  for (int j = 0; j < NW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int c0 = wave; c0 < nc; c0 += SPLIT * NC) {
+    gf8_u32x4 wv[NC][NW][4];
+    u32 sv[NC][NW];
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+      const int c = c0 + h * SPLIT;    // wave-uniform
+      if (h == 0 || c < nc) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            wv[h][j][b] = __builtin_nontemporal_load(
+                wt + ((long)j * kb + c * 4 + b) * 64);
+          sv[h][j] = __builtin_nontemporal_load(st + ((long)j * nc + c) * 64);
+        }
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+      const int c = c0 + h * SPLIT;
+      if (h == 0 || c < nc) {
+        union { gf8_u32x4 u; bf16x8 v; } xv[4][4];
+        if (live) {
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+              xv[b][w].u = xr[c * (GF8_CHUNK / 8) + b * 16 + w];
+        } else {
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+              xv[b][w].u = gf8_u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int j = 0; j < NW; ++j) {
+            // e8m0 byte b of the dword -> 2**(byte - 127) as fp32 bits
+            const float s =
+                __builtin_bit_cast(float, ((sv[h][j] >> (8 * b)) & 255u) << 23);
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+              acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  gm4_cvt8(wv[h][j][b][w], s), xv[b][w].v, acc[j], 0, 0, 0);
+          }
+      }
+    }
+  }
+
+  if constexpr (SPLIT > 1) {
+    // partial tiles [wave][NW][4 regs][64 lanes]; wave 0 adds in wave order
+    __shared__ float red[SPLIT * NW * 4 * 64];
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        red[((wave * NW + j) * 4 + r) * 64 + lane] = acc[j][r];
+    // __syncthreads() by its builtins: the header's function would be a call
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (wave != 0) return;
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float s = red[(j * 4 + r) * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < SPLIT; ++w)
+          s += red[((w * NW + j) * 4 + r) * 64 + lane];
+        acc[j][r] = s;
+      }
+  }
+  if (!live) return;
+  // lane holds C[m0 + r][n], r = 0..3: four adjacent bf16 of y row n
+  const int m0 = tile * 16 + kg * 4;
+  union { gf8_u32x2 u; u16 h[4]; } out;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float v = acc[0][r];
+    if (SWIGLU) v = v / (1.f + expf(-v)) * acc[1][r];   // silu(gate) * up
+    out.h[r] = f2bf(v);
+  }
+  *reinterpret_cast<gf8_u32x2*>(y + (long)n * M + m0) = out.u;
+}
+
+
+// ---------------------------------------------------------------------------
 // Weight-only fp8 skinny GEMM for 17 <= N <= 64 rows of x (speculative
 // verify, paged prefill tails, decode above 16 slots): gemv_fp8's packed
 // weight, scales and arguments, NT = ceil(N / 16) MFMA column tiles.
@@ -3671,6 +3844,74 @@ int gemv_moe_fp8_swiglu(void* stream, const void* table_w,
                         void* y, int F, int K, int N, int E, int xdiv) {
   return gemv_moe_fp8_launch(true, stream, table_w, table_s, idx, x, y, F,
                              K, N, E, xdiv);
+}
+
+// Routed MXFP4 decode GEMVs (gemv_moe_mx4_kernel): grid (tiles, E), the split
+// of ONE expert's tiles, so chunk owners and addition order are gemv_mx4's.
+// two: the loads of two chunks in flight per wave (same bits).
+static int gemv_moe_mx4_launch(bool swiglu, bool two, void* stream,
+                               const void* table_w, const void* table_s,
+                               const void* idx, const void* x, void* y, int M,
+                               int K, int N, int E, int xdiv) {
+  if (M <= 0 || K <= 0 || (M % 16) != 0 || (K % GF8_CHUNK) != 0 || N < 1 ||
+      N > 16 || E < 1 || E > 65535 || xdiv < 1 || !table_w || !table_s ||
+      !idx || !x || !y)
+    return -1;
+  const int tiles = M / 16;
+  dim3 grid((unsigned)tiles, (unsigned)E);
+  switch (gemv_mx4_split(tiles, K)) {
+#define GMM4_LAUNCH(S, SW, TW) \
+    hipLaunchKernelGGL((gemv_moe_mx4_kernel<S, SW, TW>), grid, \
+                       dim3(64 * S), 0, STREAM, \
+                       (const unsigned long long*)table_w, \
+                       (const unsigned long long*)table_s, (const long*)idx, \
+                       (const u16*)x, (u16*)y, M, K, N, xdiv)
+#define GMM4_CASE(S) \
+    case S: \
+      if (swiglu && two) GMM4_LAUNCH(S, true, true); \
+      else if (swiglu) GMM4_LAUNCH(S, true, false); \
+      else if (two) GMM4_LAUNCH(S, false, true); \
+      else GMM4_LAUNCH(S, false, false); \
+      break;
+    GMM4_CASE(1) GMM4_CASE(2) GMM4_CASE(4) GMM4_CASE(8)
+#undef GMM4_CASE
+#undef GMM4_LAUNCH
+    default:
+      return -1;
+  }
+  return 0;
+}
+
+// What gemv_moe_mx4 / gemv_moe_mx4_swiglu launch: one chunk's loads in
+// flight per wave, or two. One: two lost 26-28% on gate|up and gained at
+// most 2% on down at 1, 2, 4 and 8 hit experts (profiles/r23_moe_mxfp4.md).
+#define GMM4_TWO false
+
+// table_w / table_s: device u64 [E] of each expert's packed [M, K] e2m1
+// values and e8m0 scale image (ops/mx4_weight.py); idx device int64 [N]; x
+// bf16 [ceil(N / xdiv), K]; y bf16 [N, M]. Pair n reads x row n / xdiv. Rows
+// whose idx is outside [0, E) are not written.
+int gemv_moe_mx4(void* stream, const void* table_w, const void* table_s,
+                 const void* idx, const void* x, void* y, int M, int K, int N,
+                 int E, int xdiv) {
+  return gemv_moe_mx4_launch(false, GMM4_TWO, stream, table_w, table_s, idx,
+                             x, y, M, K, N, E, xdiv);
+}
+
+// the packed gate|up [2F, K] experts -> y [N, F]
+int gemv_moe_mx4_swiglu(void* stream, const void* table_w,
+                        const void* table_s, const void* idx, const void* x,
+                        void* y, int F, int K, int N, int E, int xdiv) {
+  return gemv_moe_mx4_launch(true, GMM4_TWO, stream, table_w, table_s, idx,
+                             x, y, F, K, N, E, xdiv);
+}
+
+// benchmark entry (scripts/moemx4bench.py): chunks in flight forced
+int gemv_moe_mx4_ab(void* stream, int swiglu, int two, const void* table_w,
+                    const void* table_s, const void* idx, const void* x,
+                    void* y, int M, int K, int N, int E, int xdiv) {
+  return gemv_moe_mx4_launch(swiglu != 0, two != 0, stream, table_w, table_s,
+                             idx, x, y, M, K, N, E, xdiv);
 }
 
 

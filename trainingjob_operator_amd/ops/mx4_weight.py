@@ -29,7 +29,7 @@ tile t next to up tile t.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
@@ -103,6 +103,35 @@ class Mx4Weight:
         q = grid[(code & 7).long()]
         q = torch.where(code >= 8, -q, q)
         return q * self.scales().repeat_interleave(MX_BLOCK, dim=1)
+
+
+@dataclass
+class Mx4ExpertTables:
+    """What the routed MXFP4 GEMVs (hip/ops.hip gemv_moe_mx4_kernel) read for
+    one weight of every expert of an MoE layer: device int64 [E] tables of
+    the experts' packed values and of their scale images. The Mx4Weights are
+    held here so that the pointers stay valid as long as the tables do."""
+    experts: List[Mx4Weight]
+    w: torch.Tensor               # int64 [E]: packed.data_ptr()
+    s: torch.Tensor               # int64 [E]: scale.data_ptr()
+    M: int
+    K: int
+    gate_up: bool
+
+
+def mx4_expert_tables(experts: List[Mx4Weight]) -> Mx4ExpertTables:
+    """Tables over same-shaped Mx4Weights living on one device."""
+    e0 = experts[0]
+    assert all((e.M, e.K, e.gate_up) == (e0.M, e0.K, e0.gate_up)
+               and e.packed.device == e0.packed.device
+               and e.packed.is_contiguous() and e.scale.is_contiguous()
+               for e in experts)
+    dev = e0.packed.device
+    w = torch.tensor([e.packed.data_ptr() for e in experts],
+                     dtype=torch.int64, device=dev)
+    s = torch.tensor([e.scale.data_ptr() for e in experts],
+                     dtype=torch.int64, device=dev)
+    return Mx4ExpertTables(list(experts), w, s, e0.M, e0.K, e0.gate_up)
 
 
 def quantize_mx4(weight: torch.Tensor,

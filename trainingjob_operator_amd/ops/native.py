@@ -110,6 +110,13 @@ def load(require: bool = True) -> Optional[ctypes.CDLL]:
     # table of scales, idx int64 [N], x, y, M | F, K, N <= 16, E, xdiv)
     _sig(lib.gemv_moe_fp8, [vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
     _sig(lib.gemv_moe_fp8_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
+    # routed MXFP4 GEMVs: the same arguments, the tables being of the packed
+    # e2m1 values and of the e8m0 scale images; gemv_moe_mx4_ab(stream,
+    # swiglu, two, ...) forces the chunks in flight, for benchmarks
+    _sig(lib.gemv_moe_mx4, [vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
+    _sig(lib.gemv_moe_mx4_swiglu, [vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)
+    _sig(lib.gemv_moe_mx4_ab, [vp, i, i, vp, vp, vp, vp, vp, i, i, i, i, i],
+         i)
     _sig(lib.attn_decode, [vp, vp, vp, vp, vp, vp, vp,
                            i, i, i, i, i, f], i)
     _sig(lib.rope_cache, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i], i)

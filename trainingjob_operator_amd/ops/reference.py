@@ -626,3 +626,18 @@ def decode_moe_swiglu_fp8(x: torch.Tensor, idx: torch.Tensor, tables, F: int,
     """Twin of gemv_moe_fp8_swiglu over the experts' gate|up weights."""
     assert (tables.M, tables.K, tables.gate_up) == (2 * F, K, True)
     return _moe_fp8(decode_swiglu_fp8, x, idx, tables, xdiv)
+
+
+def decode_moe_mx4(x: torch.Tensor, idx: torch.Tensor, tables, M: int,
+                   K: int, xdiv: int) -> torch.Tensor:
+    """Twin of hip/ops.hip gemv_moe_mx4: pair n is decode_linear_mx4 of x row
+    n // xdiv over expert idx[n]'s Mx4Weight (reads idx on the host)."""
+    assert (tables.M, tables.K, tables.gate_up) == (M, K, False)
+    return _moe_fp8(decode_linear_mx4, x, idx, tables, xdiv)
+
+
+def decode_moe_swiglu_mx4(x: torch.Tensor, idx: torch.Tensor, tables, F: int,
+                          K: int, xdiv: int) -> torch.Tensor:
+    """Twin of gemv_moe_mx4_swiglu over the experts' gate|up weights."""
+    assert (tables.M, tables.K, tables.gate_up) == (2 * F, K, True)
+    return _moe_fp8(decode_swiglu_mx4, x, idx, tables, xdiv)

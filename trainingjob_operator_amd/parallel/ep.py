@@ -21,8 +21,10 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ..ops import decode_moe_fp8, decode_moe_swiglu_fp8, swiglu
+from ..ops import (decode_moe_fp8, decode_moe_mx4, decode_moe_swiglu_fp8,
+                   decode_moe_swiglu_mx4, swiglu)
 from ..ops.fp8_weight import expert_tables, quantize_rows
+from ..ops.mx4_weight import mx4_expert_tables, quantize_mx4
 from .tp import _group_size
 
 
@@ -147,6 +149,39 @@ def quantize_expert(ex) -> bool:
     return True
 
 
+def expert_mx4(ex):
+    """An expert's (gate|up, down) Mx4Weights, unless it has none or one of
+    its three weights was written since they were made."""
+    w4 = getattr(ex, "mx4_weights", None)
+    if w4 is not None and ex.mx4_weight_versions != tuple(
+            w._version for w in _expert_weights(ex)):
+        return None
+    return w4
+
+
+@torch.no_grad()
+def quantize_expert_mx4(ex) -> bool:
+    """quantize_expert in OCP MXFP4 (ops/mx4_weight.py): gate and up
+    quantised together as the packed gate|up [2F, K] weight, down plain, the
+    dequantised values written back into the three weights (exact:
+    power-of-two block scales, one mantissa bit). False, and nothing
+    written, for a TPExpert or a shape the kernels do not take."""
+    if type(ex).__name__ != "Expert":
+        return False
+    gate, up, down = _expert_weights(ex)
+    gu4 = quantize_mx4(torch.cat([gate, up]), gate_up=True)
+    d4 = quantize_mx4(down)
+    if gu4 is None or d4 is None:
+        return False
+    g, u = gu4.dequant().chunk(2)
+    gate.copy_(g)
+    up.copy_(u)
+    down.copy_(d4.dequant())
+    ex.mx4_weights = (gu4, d4)
+    ex.mx4_weight_versions = tuple(w._version for w in (gate, up, down))
+    return True
+
+
 class TPExpert(nn.Module):
     """One SwiGLU expert with its weights TENSOR-sharded over the TP group
     (EP x TP composition: experts split across EP ranks, each expert's
@@ -238,6 +273,24 @@ class MoEMLP(nn.Module):
                                 expert_tables([w[1] for w in w8]))
         return self._fp8_ptr_tables
 
+    def _mx4_tables(self, device):
+        """_fp8_tables for the routed MXFP4 GEMVs: (gate|up, down)
+        Mx4ExpertTables, or None unless every expert carries fresh MXFP4
+        weights (expert_mx4) on `device`; rebuilt when any expert's
+        Mx4Weight is no longer the one the tables point into."""
+        w4 = [expert_mx4(ex) for ex in self.experts]
+        if any(w is None or w[0].packed.device != device for w in w4):
+            self._mx4_ptr_tables = None
+            return None
+        cached = getattr(self, "_mx4_ptr_tables", None)
+        if cached is not None and all(
+                a is w[0] and b is w[1] for a, b, w in
+                zip(cached[0].experts, cached[1].experts, w4)):
+            return cached
+        self._mx4_ptr_tables = (mx4_expert_tables([w[0] for w in w4]),
+                                mx4_expert_tables([w[1] for w in w4]))
+        return self._mx4_ptr_tables
+
     def _decode_forward(self, xt: torch.Tensor, fp8: bool = False):
         """Sync-free decode path (single process, <= 16 routed pairs):
         router topk feeds DEVICE index tensors straight into the routed
@@ -246,7 +299,9 @@ class MoEMLP(nn.Module):
         pair count, so the grouped path stays better at prefill sizes.
         With fp8 on and every expert quantised (quantize_expert) the two
         GEMVs are the expert-grouped fp8 ones (ops.decode_moe_swiglu_fp8,
-        decode_moe_fp8): each hit expert streamed once, in e4m3.
+        decode_moe_fp8): each hit expert streamed once, in e4m3. Experts
+        quantised to MXFP4 instead (quantize_expert_mx4) take the same route
+        through decode_moe_swiglu_mx4 / decode_moe_mx4, at 4.25 bits.
         Returns None when unsupported (caller falls back)."""
         H = xt.shape[-1]
         ex = self.experts[0]
@@ -276,6 +331,15 @@ class MoEMLP(nn.Module):
                 out = (z.reshape(T, self.top_k, H).float()
                        * gates[..., None]).sum(dim=1)
                 return out.to(xt.dtype)
+        t4 = self._mx4_tables(xt.device) if fp8 and t8 is None else None
+        if t4 is not None:
+            y = decode_moe_swiglu_mx4(xc, idxf, t4[0], ff, H, self.top_k)
+            z = None if y is None else decode_moe_mx4(y, idxf, t4[1], H, ff,
+                                                      1)
+            if z is not None:
+                out = (z.reshape(T, self.top_k, H).float()
+                       * gates[..., None]).sum(dim=1)
+                return out.to(xt.dtype)
         tg, tu, td = self._decode_tables(xt.device)
         y = torch.empty(N, ff, dtype=torch.bfloat16, device=xt.device)
         rc = lib.gemv_moe_swiglu(native.stream_ptr(), tg.data_ptr(),
@@ -293,9 +357,10 @@ class MoEMLP(nn.Module):
         return out.to(xt.dtype)
 
     def forward(self, x: torch.Tensor, fp8: bool = False) -> torch.Tensor:
-        """fp8: serve a decode-sized step from the experts' fp8 weights
-        where they have them (the caller's weights="fp8"; the values are
-        those of the bf16 weights, so every other path is the same model)."""
+        """fp8: serve a decode-sized step from the experts' fp8 or MXFP4
+        weights where they have them (the caller's weights="fp8" or
+        "mxfp4"; the values are those of the bf16 weights, so every other
+        path is the same model)."""
         orig_shape = x.shape
         H = orig_shape[-1]
         xt = x.reshape(-1, H)
